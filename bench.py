@@ -10,13 +10,19 @@ is resident in HBM before the timed region.  Batches are cut from the DeviceLoad
 (rank r takes perm(seed, epoch)[r::world_size], the DistributedSampler contract of training.py:291-294), `--batch`
 graphs per GPU per step whatever N is: weak scaling; value = edges over all ranks / max-over-ranks time.
 
-Beside the headline the line carries (rank 0, N=1): `sustained` (>= 2 s of steps), `fp32_mode` (the parity-mode
-step), `ref_batch_100` (the reference's batch size, config.yml:136), `cpu_baseline` (the oracle on the host cores on
-the SAME batches) with the val-MAE / prediction deltas of the fp32 and bf16 HIP paths at the trained weights.
+A plain run measures the headline only: set-up, settle phase, W warm-up steps, K timed steps, the line.  With `--full`
+the line also carries (rank 0, N=1): `sustained` (>= 2 s of steps), `fp32_mode` (the parity-mode step),
+`ref_batch_100` (the reference's batch size, config.yml:136), `other_models`, `cpu_baseline` (the oracle on the host
+cores on the SAME batches) with the val-MAE / prediction deltas of the fp32 and bf16 HIP paths at the trained weights;
+and for N > 1 `strong_scaling`.
 `--model schnet|megnet` switch to the cfg3 / cfg4 workloads (SchNet_demo on MOF-like graphs, MEGNet_demo on
 bulk-like graphs) with their own roofline kernels; the default line is cfg2.
+`--dump-outputs DIR` writes what the last timed step computed (prediction, loss, gradients, BatchNorm running
+statistics) as DIR/<name>.npy.  In front of the last timed step the model and optimizer go back to their initial state, so that
+with the same arguments that step has the same inputs in every run.
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 """
@@ -70,14 +76,14 @@ def parse():
     ap.add_argument("--gc", type=int, default=4)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="headline only: skip sustained / fp32_mode / ref_batch_100 (used for the rocprofv3 pass, so that "
-                         "the per-kernel averages of the trace are those of the measured workload)")
+                    help="with --full: skip sustained / fp32_mode / ref_batch_100 / other_models (a plain run skips them anyway; "
+                         "used for the rocprofv3 pass, so that the per-kernel averages of the trace are those of the measured workload)")
     ap.add_argument("--sustain-s", type=float, default=2.0)
     ap.add_argument("--settle-s", type=float, default=1.0,
                     help="MINIMUM seconds of untimed steps in front of the warm-up (0 = none); the settle phase then goes on until three "
                          "consecutive 8-step groups agree within 3 %% or --settle-cap-s is reached")
     ap.add_argument("--settle-cap-s", type=float, default=3.0, help="upper bound of the settle phase in seconds")
-    ap.add_argument("--fp32-leg", action="store_true", help="with --no-extras: still time the fp32 (parity-mode) step (other_models legs)")
+    ap.add_argument("--fp32-leg", action="store_true", help="time the fp32 / bf16x3 (parity-mode) steps without the other --full legs (other_models legs)")
     ap.add_argument("--targets", default="composition", choices=["composition", "noise"],
                     help="composition: the standardised mean atomic number of a graph (a target the models can fit, so that val-MAE "
                          "deltas discriminate); noise: the N(0,1) targets of the SURVEY 8d recipe")
@@ -112,6 +118,13 @@ def parse():
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--dataset-cache", default=os.path.join(os.environ.get("TMPDIR", "/tmp"), "mdl_bench_data"),
                     help="directory for the flat on-disk copy of the synthetic dataset ('' = always regenerate)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: sustained / ref_batch_100 / fp32_mode / bf16x3_mode, other_models, "
+                         "cpu_baseline and (N > 1) strong_scaling.  Off by default: a plain run sets up, warms up, times the "
+                         "K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the LAST timed step computed as DIR/<name>.npy (float32): the "
+                         "prediction, the loss, every parameter's gradient and the BatchNorm running statistics")
     return ap.parse_args()
 
 
@@ -213,12 +226,14 @@ def settle_phase(step, stream, dev, use_dist, settle_s, cap_s):
     return n, groups
 
 
-def timed_region(step, step_ids, warmup, steps, dev, use_dist, ev_stride, barrier, run_in=0):
+def timed_region(step, step_ids, warmup, steps, dev, use_dist, ev_stride, barrier, run_in=0, before_last=None):
     """W untimed warm-up steps, then EXACTLY K timed steps bracketed by barrier + device synchronisation on both sides; the
     MAX over ranks of the host-clock time and the SUM over ranks of the edges.  Returns a dict.
     `run_in` (diagnosis only, default 0): that many of the W warm-up steps are enqueued BEHIND the barrier, and the dict also
     carries `elapsed_dev` = device-event time from the start mark (recorded behind them) to the end mark — the K steps as the
-    device sees them when its launch queue is not empty at the start."""
+    device sees them when its launch queue is not empty at the start.
+    `before_last` (optional): called in front of the last timed step (bench: the model / optimizer state reset that makes the
+    inputs of that step the same in every run)."""
     total = warmup + steps
     run_in = max(0, min(run_in, warmup))
     for i in range(warmup - run_in):
@@ -242,6 +257,8 @@ def timed_region(step, step_ids, warmup, steps, dev, use_dist, ev_stride, barrie
         k = i - warmup
         ev_on = k % ev_stride == ev_phase
         th = time.perf_counter()
+        if before_last is not None and i == total - 1:
+            before_last()
         e, n = step(step_ids[i], ev_on, step_ids[i + 1] if i + 1 < total else step_ids[0])
         host_ms.append(round((time.perf_counter() - th) * 1e3, 3))
         edges += e
@@ -368,9 +385,11 @@ def main():
               "gcn": {"gmr_fwd": []}, "mpnn": {"nnconv_fwd": []}}[args.model]
 
     prefetch = not args.no_prefetch
+    keep_last = bool(args.dump_outputs)
 
     def make_step(model, dp, opt, dtype):
         pending = {}                                 # ids (bytes) -> handle of the batch being assembled one step ahead
+        last = {}                                    # --dump-outputs: what the latest step computed (detached)
 
         def step(ids, timed, next_ids=None):
             ahead = pending.pop(ids.tobytes(), None)
@@ -390,10 +409,13 @@ def main():
                 loss = ops.loss("l1_loss", out, batch.y)
                 ops.backward(loss)
             ops.KERNEL_EVENTS = None
+            if keep_last:
+                last["prediction"], last["loss"] = out.detach(), loss.detach()
             if dp.reduce_grads_async(force=use_dist):
                 dp.finish()
             opt.step()
             return batch.num_edges, batch.num_nodes
+        step.last = last
         return step
 
     step = make_step(model, dp, opt, cdt)
@@ -401,6 +423,21 @@ def main():
     barrier = make_barrier(dev, use_dist)
 
     model.train()
+    # The inputs of the LAST timed step are made the same in every run: in front of it the model goes back to this state and
+    # the optimizer to its initial one (AdamW: zero moments and step).  Without the reset that step would start from weights
+    # trained by every step before it — a number of settle steps that varies from run to run, and each step's rounding
+    # (atomic accumulation order) amplified by AdamW into whole +-lr updates: two runs end 10-20 % apart in the weights.
+    # The reset is a few copy / fill launches, once per run (--dump-outputs writes what that step computed); it also runs once
+    # in front of the warm-up steps, so that the first use of its kernels (code-object loading: 10-30 ms) is not timed.
+    state_now = list(model.state_dict().values())
+    state0 = [v.detach().clone() for v in state_now]
+
+    def reset_state():
+        with torch.no_grad():
+            torch._foreach_copy_(state_now, state0)
+            opt_state = [v for st in opt.state.values() for v in st.values() if torch.is_tensor(v)]
+            if opt_state:
+                torch._foreach_zero_(opt_state)
     # Settle phase (untimed, before the W warm-up steps): a fresh process sees a window of 100-200 ms, a few dozen steps
     # after its first launches, in which every kernel runs 2-4x slower, and a leg of 900 launches per step with varying batch
     # sizes (MEGNet) spends its first dozens of steps on first-use costs — hipBLASLt heuristics per GEMM shape, hipMalloc until
@@ -434,10 +471,13 @@ def main():
             step(step_ids[0], False, step_ids[k])          # (assembles batch k on the side stream ...)
             step(step_ids[k], False, step_ids[0])          # (... and steps on it)
             settle_steps += 2
+    reset_state()
     # (prefetch: every step also starts the assembly of the batch that follows on a side stream — the first timed batch during
     # the last warm-up step, and the last timed step one more (unused) batch, so that the K timed steps contain K assemblies)
     ev_stride = args.event_stride or (4 if args.steps >= 8 else 1)
-    tr = timed_region(step, step_ids, args.warmup, args.steps, dev, use_dist, ev_stride, barrier, run_in=args.run_in)
+    tr = timed_region(step, step_ids, args.warmup, args.steps, dev, use_dist, ev_stride, barrier, run_in=args.run_in,
+                      before_last=reset_state)
+    del state0, state_now
     if args.collector == "freeze":
         gc.unfreeze()
     if gc_was:
@@ -445,10 +485,12 @@ def main():
     elapsed, elapsed_max, edges_all = tr["elapsed"], tr["elapsed_max"], tr["edges_all"]
     edges, nodes, by4 = tr["edges"], tr["nodes"], tr["by4"]
     ev_edges, ev_nodes, ev_steps = tr["ev_edges"], tr["ev_nodes"], tr["ev_steps"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.last, model)
 
-    # ---- strong scaling beside it (N > 1): the GLOBAL batch fixed at the one-GPU size, B / N graphs per GPU ----
+    # ---- strong scaling beside it (--full, N > 1): the GLOBAL batch fixed at the one-GPU size, B / N graphs per GPU ----
     strong = None
-    if (world > 1 or args.force_strong) and args.strong_steps > 0:
+    if ((world > 1 and args.full) or args.force_strong) and args.strong_steps > 0:
         div = world if world > 1 else 2
         Bs = max(1, B // div)
         s_stream = batch_stream(DeviceLoader(ds, tr_idx, Bs, shuffle=True, seed=args.seed + 1, rank=rank, world_size=world), Bs)
@@ -621,7 +663,8 @@ def main():
                                                                                              "launches", "algorithmic_bytes_per_launch")}
                                            for k in have}
 
-    if world == 1 and not args.no_extras:
+    full_extras = args.full and not args.no_extras
+    if world == 1 and full_extras:
         from matdeeplearn_amd.training import GraphedStep
 
         def run_for(step_fn, it, min_s=None, n=None, ahead=False):
@@ -721,7 +764,7 @@ def main():
 
     # ---- the parity modes: same model, same batches, compute_dtype fp32 (exact products) and — CGCNN, whose conv kernels have
     # the form — bf16x3 (fp32 storage, the conv products as three bf16 MFMAs on (hi, lo)-split operands) ---------------------
-    if world == 1 and args.dtype == "bf16" and (args.fp32_leg or not args.no_extras):
+    if world == 1 and args.dtype == "bf16" and (args.fp32_leg or full_extras):
         # (bf16x3: split conv kernels for CGCNN at C = 64 / (96, 128]; for every model the Linears' weight gradients on split operands)
         for mode in ("fp32", "bf16x3"):
             torch.manual_seed(args.seed)
@@ -747,15 +790,43 @@ def main():
 
     # ---- the other BASELINE configurations as short legs of the same run (cfg3 SchNet_demo, cfg4 MEGNet_demo, the cfg5 members):
     # one sub-process each, a dataset of two batches, a few timed steps, bf16 parity on a small held-out sample ----------
-    if world == 1 and args.model == "cgcnn" and not args.no_extras and not args.no_other_models:
+    if world == 1 and args.model == "cgcnn" and full_extras and not args.no_other_models:
         res["other_models"] = other_models(args)
 
     # ---- CPU baseline: the oracle (pure-torch restatement of the reference path) on host cores ----
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args, ds, model, cls_name, mkw, step_ids[args.warmup:], va_idx)
     if use_dist:
         dist.destroy_process_group()
     print(json.dumps(res))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, last, model):
+    """--dump-outputs: what the last timed step computed from its inputs (the initial model and optimizer state, its batch) —
+    the prediction, the loss, every parameter's gradient and the BatchNorm running statistics its forward moved — as float32
+    DIR/<name>.npy.  Not the weights the optimizer then wrote: AdamW's first step from zero moments moves every weight by
+    lr * g / |g|, so wherever a gradient is within rounding of zero the sign of a whole lr-sized update is decided by the
+    rounding.  Beyond 64 MB in all, each array larger than its share of the budget is cut to a fixed, seeded sample of its
+    elements (sorted flat indices)."""
+    arrays = {"prediction": last["prediction"], "loss": last["loss"]}
+    for k, p in model.named_parameters():
+        if p.grad is not None:
+            arrays["grad." + k] = p.grad.detach()
+    for k, b in model.named_buffers():
+        if b.is_floating_point():
+            arrays["buffer." + k] = b.detach()
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    share = DUMP_LIMIT_BYTES // 4 // len(arrays)
+    cut = sum(a.size for a in arrays.values()) * 4 > DUMP_LIMIT_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        if cut and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(a, dtype=np.float32))
+    print("[bench] %d arrays written to %s" % (len(arrays), out_dir), file=sys.stderr)
 
 
 def other_models(args):
@@ -771,7 +842,7 @@ def other_models(args):
         # 20 timed steps behind a settle phase that runs until the step time has converged (>= 0.5 s, three 8-step groups within
         # 3 %, cap 3 s): round 4's 6 steps behind a fixed 0.3 s timed a fresh box's first-use costs (driver: 54.4 ms/step for
         # the MEGNet leg against 19.3 on a warm box)
-        cmd = [sys.executable, os.path.abspath(__file__), "--model", model, "--steps", "20", "--warmup", "3", "--settle-s", "0.5",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--model", model, "--steps", "20", "--warmup", "3", "--settle-s", "0.5",
                "--settle-cap-s", "3.0", "--no-extras", "--fp32-leg", "--graphs", str(int(B * 1.25 / 0.8) + 64), "--cpu-steps", "0",
                "--dataset-cache", args.dataset_cache, "--seed", str(args.seed), "--no-other-models", "--targets", args.targets] + extra + [a for o in args.ops for a in ("--ops", o)]
         t0 = time.time()

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = [pytest.mark.gpu, pytest.mark.last]
@@ -202,3 +203,37 @@ def test_bench_megnet_leg_reproduces_in_fresh_processes(tmp_path):
     # reproducibility test) AND on the 20-step means, the figure the driver line carries
     assert max(med) <= 1.10 * min(med), med
     assert max(ms) <= 1.10 * min(ms), ms
+
+
+def test_bench_plain_run_dumps_the_same_outputs_in_fresh_processes(tmp_path):
+    """A plain bench.py run (no --full) times the headline only and, with --dump-outputs, writes what its last timed step
+    computed.  The settle phase trains a varying number of steps and AdamW turns every step's rounding into lr-sized weight
+    updates, so the model and optimizer state are reset in front of that step: two fresh processes with the kernels in
+    deterministic mode must dump the same arrays, and a third in the default (atomic) mode the same to rounding — the
+    prediction to 1e-2 of its scale (bf16), the loss to 1e-4, every gradient and BatchNorm statistic to 5e-2 of its scale
+    plus 1e-3 of the largest gradient (a bias gradient that is a near-cancelling sum of large terms moves by a few % of its own
+    small scale with the summation order; without the reset the gradients differ by 10-45 %)."""
+    runs = []
+    for i, mode in enumerate(("deterministic=1", "deterministic=1", "deterministic=0")):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--graphs", "640", "--batch", "256", "--steps", "3",
+                            "--warmup", "2", "--ops", mode, "--dataset-cache", str(tmp_path), "--dump-outputs", str(d)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(line) == 1, r.stdout[-2000:] + r.stderr[-2000:]
+        res = json.loads(line[0])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["value"] > 0
+        assert not {"sustained", "ref_batch_100", "fp32_mode", "other_models", "cpu_baseline", "strong_scaling"} & set(res)
+        runs.append({f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))})
+    a, b, c = runs
+    assert set(a) == set(b) == set(c) and {"prediction", "loss"} <= set(a)
+    assert any(k.startswith("grad.") for k in a) and any(k.startswith("buffer.") for k in a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["prediction"].size == 256 and a["loss"].size == 1
+    gmax = max(float(np.abs(v).max()) for k, v in a.items() if k.startswith("grad."))
+    for k in a:
+        assert a[k].dtype == np.float32 and a[k].shape == b[k].shape == c[k].shape, k
+        assert np.array_equal(a[k], b[k]), k
+        s = float(np.abs(a[k]).max()) + 1e-12
+        bound = {"prediction": 1e-2 * s, "loss": 1e-4 * s}.get(k, 5e-2 * s + 1e-3 * gmax)
+        assert float(np.abs(a[k] - c[k]).max()) <= bound, (k, float(np.abs(a[k] - c[k]).max()), s, gmax)

@@ -8,7 +8,9 @@
   cfg4  bulk-like graphs, MEGNet_demo hyper-parameters (config.yml:184-205: dims 100, 4 blocks, gc_fc_count 1)
   cfg5  surface-like slabs, the five-model ensemble driver on the device against the same driver on the oracle
 
-Tolerances (stated once): fp32 predictions 1e-4 of the tensor scale, |dMAE| < 1e-5; fp32 gradients no worse than
+Tolerances (stated once): fp32 predictions 1e-4 of the tensor scale and |dMAE| < 1e-5 against the oracle in fp64 (the fp32
+oracle's own rounding error reaches that size: MEGNet_demo's train-mode prediction differs from fp64 by 1e-4 of its scale on 16
+CPU threads and 3e-3 on one, the HIP path by 2e-5); fp32 gradients no worse than
 50 x the fp32-CPU error against an fp64 truth (floor 2e-4 of the scale; mse loss so that the gradient is smooth); bf16 predictions 5e-2 of the scale,
 bf16 kernel outputs / gradients 3e-2 of the scale (inputs pre-rounded to bf16 on both sides).
 """
@@ -56,8 +58,9 @@ def _close(a, b, rel, what=""):
 
 
 def _model_parity(name, kw, ds, ids, grads=True):
-    """fp32 product vs fp32 oracle (same state_dict, same batch): train-mode prediction, gradients against the fp64
-    oracle, eval-mode MAE; then the bf16 product against the same oracle prediction."""
+    """fp32 product vs the oracle (same state_dict, same batch): train-mode prediction and gradients against the fp64
+    oracle (gradients no worse than a multiple of the fp32 oracle's error), eval-mode prediction / MAE against the fp64
+    oracle; then the bf16 product against the fp32 oracle's prediction."""
     from matdeeplearn_amd import models
     torch.manual_seed(0)
     ref_model = getattr(omodels, name)(ds, **kw)
@@ -65,22 +68,22 @@ def _model_parity(name, kw, ds, ids, grads=True):
     assert list(model.state_dict()) == list(ref_model.state_dict())
     model.load_state_dict(ref_model.state_dict())
     model.to(DEV)
+    m64 = copy.deepcopy(ref_model).double()
     bc, bg = _batches(ds, ids)
-    ref_model.train(); model.train()
+    b64 = types.SimpleNamespace(**{k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v)
+                                   for k, v in vars(bc).items() if not k.startswith("_")})
+    b64.edge_index = bc.edge_index
+    ref_model.train(); model.train(); m64.train()
     # (mse for the gradient comparison: the l1 gradient is sign(out - y), which flips on rounding noise whenever a
     # prediction happens to sit on its target — a discrete jump no tolerance can absorb)
     ref = ref_model(bc)
     torch.nn.functional.mse_loss(ref, bc.y).backward()
     out = model(bg)
     torch.nn.functional.mse_loss(out, bg.y).backward()
-    _close(out, ref, 1e-4, name + " fp32 train prediction")
+    out64 = m64(b64)
+    _close(out, out64, 1e-4, name + " fp32 train prediction")
     if grads:
-        m64 = copy.deepcopy(ref_model).double()
-        m64.zero_grad()
-        b64 = types.SimpleNamespace(**{k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v)
-                                       for k, v in vars(bc).items() if not k.startswith("_")})
-        b64.edge_index = bc.edge_index
-        torch.nn.functional.mse_loss(m64(b64), b64.y).backward()
+        torch.nn.functional.mse_loss(out64, b64.y).backward()
         rg, g64 = dict(ref_model.named_parameters()), dict(m64.named_parameters())
         gmax = max(float(v.grad.abs().max()) for v in g64.values() if v.grad is not None)    # floor for near-zero gradients
         for k, p in model.named_parameters():
@@ -94,14 +97,15 @@ def _model_parity(name, kw, ds, ids, grads=True):
             # gradient a sum over ~1e8 (edge, channel) masks, and a pre-activation within rounding of 0 flips its mask
             # between two fp32 summation orders — a discrete jump the CPU-vs-fp64 error does not see)
             assert gpu_err <= max(50.0 * cpu_err, 2e-4 * s, 2e-4 * gmax), (name, k, gpu_err, cpu_err, s, gmax)
-    # weights as they are after construction; BatchNorm buffers moved by the one training forward on BOTH sides
-    ref_model.eval(); model.eval()
+    # weights as they are after construction; BatchNorm buffers moved by the one training forward on EVERY side
+    ref_model.eval(); model.eval(); m64.eval()
     with torch.no_grad():
-        pr, pg_ = ref_model(bc), model(bg)
+        pr, pg_, p64 = ref_model(bc), model(bg), m64(b64)
         mae_ref = float(torch.nn.functional.l1_loss(pr, bc.y))
         mae = float(torch.nn.functional.l1_loss(pg_, bg.y))
-    _close(pg_, pr, 1e-4, name + " fp32 eval prediction")
-    assert abs(mae - mae_ref) < 1e-5 * max(1.0, abs(mae_ref)), (name, mae, mae_ref)
+        mae64 = float(torch.nn.functional.l1_loss(p64, b64.y))
+    _close(pg_, p64, 1e-4, name + " fp32 eval prediction")
+    assert abs(mae - mae64) < 1e-5 * max(1.0, abs(mae64)), (name, mae, mae64)
     # bf16 compute mode against the fp32 oracle
     m16 = getattr(models, name)(ds, compute_dtype="bf16", **kw)
     m16.load_state_dict(ref_model.state_dict())

@@ -1,7 +1,7 @@
 #!/bin/bash
 # headline bench with and without the cost-balanced node ranges of the backward (one box session)
 for b in 1 0; do
-  MDL_CG_BALANCE=$b python bench.py --no-cpu-baseline --no-other-models 2>/dev/null | tail -1 > /tmp/b.json
+  MDL_CG_BALANCE=$b python bench.py --full --no-cpu-baseline --no-other-models 2>/dev/null | tail -1 > /tmp/b.json
   python - $b <<'PY'
 import json, sys
 d = json.load(open("/tmp/b.json"))

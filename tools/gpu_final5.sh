@@ -10,7 +10,7 @@ for i in 1 2; do
   grep -E "passed|failed" $OUT/pytest_$i.log | tail -1
 done
 ( timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ) | tee $OUT/smoke.log
-timeout 900 python bench.py 2> $OUT/bench_err.log | tail -1 > $OUT/bench_line.json
+timeout 900 python bench.py --full 2> $OUT/bench_err.log | tail -1 > $OUT/bench_line.json
 python - $OUT/bench_line.json <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # headline bench with and without the fused post-FC head (one box session): timed steps, 2-s sustained eager / replay legs
 for b in ${@:-1 0}; do
-  MDL_MLP_HEAD=$b python bench.py --no-cpu-baseline --no-other-models 2>/dev/null | tail -1 > /tmp/b.json
+  MDL_MLP_HEAD=$b python bench.py --full --no-cpu-baseline --no-other-models 2>/dev/null | tail -1 > /tmp/b.json
   python - $b <<'PY'
 import json, sys
 d = json.load(open("/tmp/b.json"))

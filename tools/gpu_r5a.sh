@@ -13,7 +13,7 @@ rm -rf $OUT/prof_small
 tail -2 $OUT/small.log
 cd $GRAFT_REPO_ROOT
 timeout 300 python tools/bench_small.py > $OUT/small_noprof.log 2>&1; tail -1 $OUT/small_noprof.log
-timeout 900 python bench.py > $OUT/bench.log 2>&1
+timeout 900 python bench.py --full > $OUT/bench.log 2>&1
 grep -h '^{"metric"' $OUT/bench.log > $OUT/bench_line.json
 python - $OUT/bench_line.json <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 timeout 1500 python -m pytest tests -m gpu -q -x 2>&1 | tail -30 > $OUT/pytest.log; tail -3 $OUT/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 900 python bench.py > $OUT/bench.log 2>&1
+timeout 900 python bench.py --full > $OUT/bench.log 2>&1
 grep -h '^{"metric"' $OUT/bench.log > $OUT/bench_line.json
 python - $OUT/bench_line.json <<'PY'
 import json, sys

@@ -24,7 +24,7 @@ print('host enqueue', c['host_enqueue_ms_per_step'])" | tee -a $OUT/log.txt
 echo "== kernels" | tee -a $OUT/log.txt
 timeout 300 python tools/bench_kernels.py --which fwd,bwd --iters 20 2>&1 | grep -E "^(N=|fwd|bwd|bwd_node):|rror" | tee -a $OUT/log.txt
 echo "== full default bench (driver command)" | tee -a $OUT/log.txt
-timeout 1500 python bench.py > $OUT/bench_full.log 2>&1
+timeout 1500 python bench.py --full > $OUT/bench_full.log 2>&1
 grep '^{"metric"' $OUT/bench_full.log > $OUT/bench_line.json
 python - <<'PY' | tee -a $OUT/log.txt
 import json,os

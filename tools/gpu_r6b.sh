@@ -11,7 +11,7 @@ import json,sys; j=json.loads(sys.stdin.read()); c=j['config']; s=j.get('sustain
 print('ms/step', j['ms_per_step'], 'by4', c['ms_per_step_by_4'], 'mallocs', c['device_mallocs'], 'settle', c['settle_ms_per_step_by_8'][-2:], 'k3', j['roofline']['avg_launch_us'], '| sustained', s.get('ms_per_step'), 'mallocs', s.get('device_mallocs'), 'steps', s.get('steps'))"; }
 for conf in "roundup_power2_divisions:8" "roundup_power2_divisions:2" "roundup_power2_divisions:1" "expandable_segments:True" "roundup_power2_divisions:4"; do
   echo "== allocator $conf" | tee -a $OUT/log.txt
-  PYTORCH_ALLOC_CONF=$conf PYTORCH_HIP_ALLOC_CONF=$conf PYTORCH_CUDA_ALLOC_CONF=$conf timeout 600 python bench.py --no-cpu-baseline --no-other-models 2>$OUT/err.txt | grep '^{"metric"' | line | tee -a $OUT/log.txt
+  PYTORCH_ALLOC_CONF=$conf PYTORCH_HIP_ALLOC_CONF=$conf PYTORCH_CUDA_ALLOC_CONF=$conf timeout 600 python bench.py --full --no-cpu-baseline --no-other-models 2>$OUT/err.txt | grep '^{"metric"' | line | tee -a $OUT/log.txt
   tail -2 $OUT/err.txt | cut -c1-300 >> $OUT/log.txt
 done
 for g in off freeze on; do

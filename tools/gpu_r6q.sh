@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 for r in 1 2; do
   ( timeout 1500 python -m pytest tests -m gpu -x -q --timeout 900 2>&1 | tail -3 ) | tee -a $OUT/log.txt
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench$r.json
+  timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench$r.json
   python - $OUT/bench$r.json <<'PY' | tee -a $OUT/log.txt
 import json,sys
 j=json.load(open(sys.argv[1])); c=j["config"]

@@ -7,8 +7,8 @@ export TMPDIR=/tmp
 ( timeout 1500 python -m pytest tests -m gpu -q --timeout 600 --maxfail=8 2>&1 | grep -vE "^\s*$" | tail -40 ) > $OUT/pytest.log
 grep -E "passed|failed" $OUT/pytest.log | tail -2
 ( timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 ) > $OUT/smoke.log; tail -1 $OUT/smoke.log
-timeout 900 python bench.py 2>/dev/null | tail -1 > $OUT/bench_cgcnn.json; cut -c1-300 $OUT/bench_cgcnn.json
-for m in schnet megnet; do timeout 900 python bench.py --model $m --cpu-steps 1 2>/dev/null | tail -1 > $OUT/bench_$m.json; cut -c1-200 $OUT/bench_$m.json; done
+timeout 900 python bench.py --full 2>/dev/null | tail -1 > $OUT/bench_cgcnn.json; cut -c1-300 $OUT/bench_cgcnn.json
+for m in schnet megnet; do timeout 900 python bench.py --full --model $m --cpu-steps 1 2>/dev/null | tail -1 > $OUT/bench_$m.json; cut -c1-200 $OUT/bench_$m.json; done
 cd /tmp
 for m in cgcnn schnet megnet; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$m -o t -- python $GRAFT_REPO_ROOT/bench.py --model $m --no-cpu-baseline --no-extras > $OUT/prof_$m.log 2>&1

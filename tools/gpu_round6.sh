@@ -6,7 +6,7 @@ TAG=${1:-r06}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 NO_EXP=1 NO_BENCH=1 bash tools/gpu_suite.sh $TAG
-timeout 900 python bench.py 2> $OUT/bench_err.log | tail -1 > $OUT/bench_line.json; cut -c1-300 $OUT/bench_line.json
+timeout 900 python bench.py --full 2> $OUT/bench_err.log | tail -1 > $OUT/bench_line.json; cut -c1-300 $OUT/bench_line.json
 bash tools/gpu_prof.sh $TAG/prof_cgcnn | tee $OUT/prof_cgcnn.txt | head -12
 bash tools/gpu_prof.sh $TAG/prof_schnet --model schnet --steps 20 --warmup 3 --settle-s 0.5 --settle-cap-s 3.0 | tee $OUT/prof_schnet.txt | head -8
 bash tools/gpu_prof.sh $TAG/prof_x3 --dtype bf16x3 --steps 10 --warmup 3 --settle-s 0.5 --settle-cap-s 2.0 | tee $OUT/prof_x3.txt | head -10
