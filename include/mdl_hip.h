@@ -539,6 +539,30 @@ int mdl_edge_mul(const void* a, const int32_t* ia, const void* b, const int32_t*
  * src 8-byte, hi / lo 4-byte aligned. */
 int mdl_split_bf16(const float* src, void* hi, void* lo, int64_t n, mdlStream_t stream);
 
+/* ---- N2: crystal graphs from positions (the dataset builder) ----------------------------------------------------------
+ * Replaces the per-structure graph rule of matdeeplearn/process/process.py:258-305 (ase get_all_distances(mic=True),
+ * threshold_sort, dense_to_sparse, add_self_loops), :385-388 and :540-559, :594-605 (one-hot degree), for G structures in one
+ * call, as matdeeplearn_amd/process/graph.py restates it on the host:
+ *   d[i, j]  fp64 minimum-image distance (periodic vectors lattice-reduced, basis completed for 1-D / 2-D periodicity,
+ *            fractional difference wrapped with rint, minimum over the +-1 images of the periodic axes); plain for pbc 0;
+ *   row i keeps j when rank (d[i, j], j) <= k + 1 (ascending, ties to the lower column) and d[i, j] <= radius, minus the
+ *            entries whose fp32 value is 0 (the diagonal, coincident atoms);
+ *   edges    (i -> j, float32 d) plus one self loop per node (weight 0), stored CSR BY TARGET per graph: the in-edges of a
+ *            target with ascending sources, then its self loop.
+ * Orthorhombic and non-periodic structures give bitwise the host builder's distances; other cells the same edges with
+ * distances that may differ in the last fp64 bits.  Deterministic: the output is bitwise the same run to run.
+ * pos: [N, 3] fp64; node_ptr: [G + 1] int64 (node_ptr[0] = 0, non-decreasing, node_ptr[G] = N; the kernels clamp a bad one
+ * instead of faulting, the output is then meaningless); cell: [G, 3, 3] fp64 rows = lattice vectors; pbc: [G] int32 bitmask
+ * (bit a: axis a periodic).  k = max_neighbors in 1..64 (else MDL_E_UNSUPP), radius > 0 (else MDL_E_ARG).
+ * Outputs: edge_ptr [G + 1] int64; src / tgt [edge_capacity] int32 GRAPH-LOCAL node ids and dist [edge_capacity] fp32, of
+ * which the first edge_ptr[G] are written (edge_capacity >= N (k + 1), the bound, so no count is needed before the call);
+ * out_deg [N] int32 = kept edges of the row + 1 (the self loop).  workspace: mdl_graph_workspace_bytes(N, G, k) bytes,
+ * 256-byte aligned; a smaller workspace_bytes is rejected (MDL_E_ARG). */
+size_t mdl_graph_workspace_bytes(int64_t N, int64_t G, int max_neighbors);
+int mdl_graph_build(const double* pos, const int64_t* node_ptr, const double* cell, const int32_t* pbc, int64_t N, int64_t G,
+                    double radius, int max_neighbors, int64_t* edge_ptr, int32_t* src, int32_t* tgt, float* dist,
+                    int32_t* out_deg, int64_t edge_capacity, void* workspace, size_t workspace_bytes, mdlStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,8 @@ PROTOTYPES = {
     "mdl_cfconv_fwd": (_i32, [_vp] * 10 + [_i64, _i64, _i32, _i32, _i32, _vp]),
     "mdl_cfconv_bwd_w_scratch_bytes": (_sz, []),
     "mdl_cfconv_bwd_w": (_i32, [_vp] * 13 + [_i64, _i64, _i32, _i32, _i32, _vp]),
+    "mdl_graph_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "mdl_graph_build": (_i32, [_vp] * 4 + [_i64, _i64, ctypes.c_double, _i32] + [_vp] * 5 + [_i64, _vp, _sz, _vp]),
 }
 
 _lib = None

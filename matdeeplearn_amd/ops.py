@@ -2044,3 +2044,62 @@ def linear_relu_bn(x, weight, bias, lowp, bn_weight, bn_bias, running_mean, runn
 
 def batch_norm_train(x, weight, bias, running_mean, running_var, eps=1e-5, momentum=0.1):
     return _BatchNormTrain.apply(x, weight, bias, running_mean, running_var, eps, momentum)
+
+
+# ------------------------------------------------------------------------------------------------
+# N2 — crystal graphs from positions (process.py:258-305,540-559; csrc/graph_build.hip)
+# ------------------------------------------------------------------------------------------------
+GRAPH_MAX_NEIGHBORS = 64
+
+
+def _graph_args(pos, node_ptr, cell, pbc):
+    require_hip(pos, node_ptr, cell, pbc)
+    if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 3:
+        raise MdlError("build_graphs: pos must be [N, 3] float64 (got %s %s)" % (tuple(pos.shape), pos.dtype))
+    if node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 2:
+        raise MdlError("build_graphs: node_ptr must be [G + 1] int64 with G >= 1")
+    G = node_ptr.numel() - 1
+    if cell.dtype != torch.float64 or tuple(cell.shape) != (G, 3, 3):
+        raise MdlError("build_graphs: cell must be [G, 3, 3] float64 (got %s %s)" % (tuple(cell.shape), cell.dtype))
+    if pbc.dim() == 2 and tuple(pbc.shape) == (G, 3):                # [G, 3] booleans -> bitmask
+        pbc = (pbc.to(torch.int32) * torch.tensor([1, 2, 4], dtype=torch.int32, device=pbc.device)).sum(1, dtype=torch.int32)
+    if pbc.dtype != torch.int32 or tuple(pbc.shape) != (G,):
+        raise MdlError("build_graphs: pbc must be a [G] int32 bitmask or [G, 3] booleans")
+    return pos.contiguous(), node_ptr.contiguous(), cell.contiguous(), pbc.contiguous(), G
+
+
+def _build_graphs_launch(pos, node_ptr, cell, pbc, G, radius, max_neighbors):
+    """The HIP launches alone (no host synchronisation): edge arrays at their bound N (k + 1), edge_ptr [G + 1] on the device."""
+    N, k, dev = pos.shape[0], int(max_neighbors), pos.device
+    nbytes = lib().mdl_graph_workspace_bytes(N, G, k)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    cap = N * (k + 1) if 1 <= k <= GRAPH_MAX_NEIGHBORS else 1
+    edge_ptr = torch.empty(G + 1, dtype=torch.int64, device=dev)
+    src = torch.empty(cap, dtype=torch.int32, device=dev)
+    tgt = torch.empty(cap, dtype=torch.int32, device=dev)
+    dist = torch.empty(cap, dtype=torch.float32, device=dev)
+    out_deg = torch.empty(N, dtype=torch.int32, device=dev)
+    check(lib().mdl_graph_build(ptr(pos), ptr(node_ptr), ptr(cell), ptr(pbc), N, G, float(radius), k, ptr(edge_ptr), ptr(src),
+                                ptr(tgt), ptr(dist), ptr(out_deg), cap, ptr(ws), nbytes, stream()), "mdl_graph_build")
+    return edge_ptr, src, tgt, dist, out_deg
+
+
+def build_graphs(pos, node_ptr, cell, pbc, radius=8.0, max_neighbors=12):
+    """Graphs of G structures at once, the reference's rule (process.py:258-305: minimum-image distances, at most
+    max_neighbors nearest within radius per source row, self loops) on the device.
+      pos [N, 3] float64; node_ptr [G + 1] int64 (atoms of structure g: node_ptr[g]:node_ptr[g + 1]); cell [G, 3, 3] float64;
+      pbc [G] int32 bitmask (bit a: axis a periodic) or [G, 3] booleans.
+    Returns device tensors (edge_ptr [G + 1] int64, src [E] int32, tgt [E] int32, dist [E] float32, out_deg [N] int32): per graph
+    the edges CSR by target with graph-local node ids (in-edges by ascending source, then the self loop), dist the fp32
+    minimum-image distance, out_deg the out-degree including the self loop — exactly what process.from_structures builds on
+    the host.  Validating node_ptr and trimming the edges to E read two numbers back (two host synchronisations)."""
+    pos, node_ptr, cell, pbc, G = _graph_args(pos, node_ptr, cell, pbc)
+    N = pos.shape[0]
+    if N < 1:
+        raise MdlError("build_graphs: no atoms")
+    bad = (node_ptr[0] != 0) | (node_ptr[-1] != N) | (node_ptr[1:] < node_ptr[:-1]).any()
+    if bool(bad):
+        raise MdlError("build_graphs: node_ptr must start at 0, be non-decreasing and end at N = %d" % N)
+    edge_ptr, src, tgt, dist, out_deg = _build_graphs_launch(pos, node_ptr, cell, pbc, G, radius, max_neighbors)
+    E = int(edge_ptr[-1])
+    return edge_ptr, src[:E], tgt[:E], dist[:E], out_deg

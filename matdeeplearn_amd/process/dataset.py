@@ -402,8 +402,13 @@ def from_graphs(graphs, ys, ids, num_edge_features=50, dist_range=None):
                         num_edge_features, dist_range)
 
 
-def from_structures(structs, ys, ids, radius=8.0, max_neighbors=12, num_edge_features=50, dictionary=None):
-    """structs: iterable of dict(positions, numbers, cell, pbc) — e.g. graph.read_ase_json outputs."""
+def from_structures(structs, ys, ids, radius=8.0, max_neighbors=12, num_edge_features=50, dictionary=None, device=None):
+    """structs: iterable of dict(positions, numbers, cell, pbc) — e.g. graph.read_ase_json outputs.
+    device=None builds every graph on the host (graph.build_graph); a HIP device builds them all there in one call
+    (ops.build_graphs) and gives the same dataset, bitwise for orthorhombic and non-periodic cells.  Either way the result is
+    host-backed: callers still call .to(device)."""
+    if device is not None:
+        return _from_structures_device(structs, ys, ids, radius, max_neighbors, num_edge_features, dictionary, device)
     graphs = []
     for s in structs:
         g = pg.build_graph(s["positions"], s["numbers"], s.get("cell"), s.get("pbc"), radius, max_neighbors,
@@ -411,6 +416,26 @@ def from_structures(structs, ys, ids, radius=8.0, max_neighbors=12, num_edge_fea
         g["z"] = np.asarray(s["numbers"], dtype=np.int64)
         graphs.append(g)
     return from_graphs(graphs, ys, ids, num_edge_features)
+
+
+def _from_structures_device(structs, ys, ids, radius, max_neighbors, num_edge_features, dictionary, device):
+    """from_structures on a HIP device: vectorised packing, ops.build_graphs, one copy back, node features on the host."""
+    packed = pg.pack_structures(structs)
+    dev = torch.device(device)
+    edge_ptr, src, tgt, dist, out_deg = ops.build_graphs(
+        torch.from_numpy(packed["pos"]).to(dev), torch.from_numpy(packed["node_ptr"]).to(dev),
+        torch.from_numpy(packed["cell"]).to(dev), torch.from_numpy(packed["pbc"]).to(dev), radius, max_neighbors)
+    edge_ptr, src, tgt, dist, out_deg = (t.cpu().numpy() for t in (edge_ptr, src, tgt, dist, out_deg))
+    z = packed["numbers"]
+    if dictionary is not None:                                 # one table row per distinct Z (graph.atom_features)
+        uz = np.unique(z)
+        feats = np.asarray([dictionary[str(int(v))] for v in uz], dtype=np.float32)[np.searchsorted(uz, z)]
+    else:
+        feats = pg.atom_features(z)
+    deg = np.zeros((len(z), max_neighbors + 2), dtype=np.float32)       # graph.one_hot_degree: out-degree incl. the loop
+    deg[np.arange(len(z)), out_deg] = 1.0
+    x = np.concatenate([feats, deg], 1)
+    return GraphDataset(packed["node_ptr"], edge_ptr, x, z, src, tgt, dist, ys, ids, num_edge_features)
 
 
 def _synthetic(sizes, boxes, rng, seed, radius, max_neighbors, num_edge_features, tag):

@@ -150,3 +150,25 @@ def read_ase_json(path):
 
     return {"positions": arr(rec["positions"]), "numbers": arr(rec["numbers"]), "cell": arr(rec["cell"]),
             "pbc": arr(rec["pbc"])}
+
+
+def pack_structures(structs):
+    """Flat arrays of a list of structure dicts (positions, numbers, optional cell / pbc) for the device builder
+    (ops.build_graphs): pos [N, 3] float64, numbers [N] int64, node_ptr [G + 1] int64, cell [G, 3, 3] float64 (zeros where a
+    structure has none), pbc [G] int32 bitmask (bit a: axis a periodic; 0 where a structure has none).  Vectorised: one
+    concatenation per field, no per-structure arithmetic."""
+    structs = list(structs)
+    if not structs:
+        raise ValueError("pack_structures: no structures")
+    pos = [np.asarray(s["positions"], dtype=np.float64).reshape(-1, 3) for s in structs]
+    sizes = np.fromiter((len(p) for p in pos), dtype=np.int64, count=len(pos))
+    node_ptr = np.zeros(len(pos) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=node_ptr[1:])
+    zero_cell, no_pbc = np.zeros((3, 3)), np.zeros(3, dtype=bool)
+    cell = np.stack([np.asarray(zero_cell if s.get("cell") is None else s["cell"], dtype=np.float64).reshape(3, 3)
+                     for s in structs])
+    pbc = np.stack([np.broadcast_to(np.asarray(no_pbc if s.get("pbc") is None else s["pbc"], dtype=bool).reshape(-1), 3)
+                    for s in structs])
+    return {"pos": np.concatenate(pos), "numbers": np.concatenate([np.asarray(s["numbers"], dtype=np.int64).reshape(-1)
+                                                                  for s in structs]),
+            "node_ptr": node_ptr, "cell": cell, "pbc": (pbc.astype(np.int32) << np.arange(3, dtype=np.int32)).sum(1, dtype=np.int32)}

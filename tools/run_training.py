@@ -5,7 +5,8 @@
   python tools/run_training.py --config cfg.yml --model SchNet_demo --data synthetic:4096 --dtype bf16
 
 `--data DIR` reads a reference-style dataset directory (ASE-json structures + targets.csv, as
-/root/reference/matdeeplearn/process/process.py:234-269 expects)."""
+/root/reference/matdeeplearn/process/process.py:234-269 expects); `--graphs-on-device` builds its graphs with the HIP
+graph builder (process.from_structures(device=...)) instead of on the host."""
 import argparse
 import csv
 import os
@@ -19,7 +20,9 @@ from matdeeplearn_amd.process import from_structures, synthetic_bulk, graph as p
 from matdeeplearn_amd.training import load_config, train_regular  # noqa: E402
 
 
-def load_dataset(spec, processing):
+def load_dataset(spec, processing, device=None):
+    """device: build the graphs of `pt10` / DIR there (process.from_structures(device=...)); the synthetic sets keep their own
+    host builder."""
     r, k = processing.get("graph_max_radius", 8.0), processing.get("graph_max_neighbors", 12)
     if spec.startswith("synthetic"):
         n = int(spec.split(":")[1]) if ":" in spec else 4096
@@ -28,12 +31,12 @@ def load_dataset(spec, processing):
         z = np.load(os.path.join(os.path.dirname(__file__), "..", "tests", "golden", "pt10_dataset.npz"))
         structs = [dict(positions=z["positions"][s], numbers=z["numbers"][s], cell=z["cell"][s], pbc=z["pbc"][s])
                    for s in range(len(z["ids"]))]
-        return from_structures(structs, z["y"], [str(v) for v in z["ids"]], r, k)
+        return from_structures(structs, z["y"], [str(v) for v in z["ids"]], r, k, device=device)
     rows = list(csv.reader(open(os.path.join(spec, processing.get("target_path", "targets.csv")))))
     fmt = processing.get("data_format", "json")
     structs = [pg.read_ase_json(os.path.join(spec, "%s.%s" % (row[0], fmt))) for row in rows]
     ys = np.array([[float(v) for v in row[1:]] for row in rows], dtype=np.float32)
-    return from_structures(structs, ys, [row[0] for row in rows], r, k)
+    return from_structures(structs, ys, [row[0] for row in rows], r, k, device=device)
 
 
 def main():
@@ -45,6 +48,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=None)
     ap.add_argument("--graph-replay", default=None, choices=["auto", "True", "False"],
                     help="Training.graph_replay: run the training steps as HIP-graph replays (auto: for small batches)")
+    ap.add_argument("--graphs-on-device", action="store_true",
+                    help="build the crystal graphs of --data pt10 / DIR with the HIP graph builder instead of on the host")
     a = ap.parse_args()
     job, processing, training, mp = load_config(a.config, "Training", a.model)
     if a.epochs:
@@ -52,7 +57,7 @@ def main():
     mp["compute_dtype"] = a.dtype
     if a.graph_replay:
         training["graph_replay"] = a.graph_replay
-    ds = load_dataset(a.data, processing).to("cuda")
+    ds = load_dataset(a.data, processing, device="cuda" if a.graphs_on_device else None).to("cuda")
     edge_dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     out = train_regular("cuda", 1, ds, job, training, mp, edge_dtype=edge_dtype)
     h = out["history"]
