@@ -1,7 +1,8 @@
 """Builds experiments/lib/libmdl_hip_exp.so: the product sources (matdeeplearn_amd/csrc/*.hip) compiled with
 -DMDL_EXPERIMENTS=1, which adds the measured-negative kernel variants of experiments/csrc/ (cooperative weight-stationary
-CGConv kernels, the first edge-per-lane backward, the saved-gate pair, the W-split pair, the two-layer dense kernel, the
-dynamic tail of kernel 2 with -DMDL_EP2_TAIL=25) and their environment switches.  Not part of build(); run by hand:
+CGConv kernels, the first edge-per-lane backward, the saved-gate pair, the W-split pair, the two-layer dense kernel) and
+their environment switches (the dynamic tail of kernel 2 was measured at commit 9c7faa6 and removed after it).  Not part
+of build(); run by hand:
 
     python experiments/build.py [extra hipcc flags]
     MDL_HIP_LIB=experiments/lib/libmdl_hip_exp.so python -m pytest experiments/test_experiments.py -m gpu

@@ -36,10 +36,7 @@ constexpr int G_ = 50, GH = G_ / 2;           // Gaussians per edge (the referen
 constexpr int KE = 64, EKS = KE + 8;          // K of GEMM1 (G + bias column, padded); row stride of the rbf tile (halfwords)
 constexpr int W1S = KE + 8;                   // row stride of the packed layer-1 weights in LDS (halfwords)
 constexpr int DCS = 32 * 8 + 32;              // one chunk row of the message block: 32 edges x 8 bytes + pad
-#ifndef MDL_CF_NWAVE
-#define MDL_CF_NWAVE 8
-#endif
-constexpr int NWAVE = MDL_CF_NWAVE, NT = NWAVE * WAVE;
+constexpr int NWAVE = 8, NT = NWAVE * WAVE;
 constexpr int NJ = (32 * GH + WAVE - 1) / WAVE;           // dwords of an rbf tile per lane
 constexpr int OFF_ET = 0, OFF_DP = 32 * EKS * 2, OFF_TSL = OFF_DP + 8 * DCS, OFF_STASH = OFF_TSL + 64;
 constexpr int WAVE_BYTES = OFF_STASH + NJ * WAVE * 4;     // (the stash: the NEXT tile's rbf dwords, parked in LDS once they have arrived)
@@ -286,9 +283,7 @@ __global__ __launch_bounds__(NT, 2) void cfconv_fwd_kernel(Params p) {
             }
             // every load of this tile (and the next tile's operands) has had GEMM1 to arrive; from here on the tile only stores
             CF_TMARK(1);
-#ifndef MDL_CF_NOWAIT
             __builtin_amdgcn_s_waitcnt(0x0F70);                       // vmcnt(0)
-#endif
             CF_TMARK(2);
             park(nxt);
             // one-hot operands of the by-target reduction (k-slot q of k-step ks = edge slot 16 ks + 8 (q >> 2) + 4 h + (q & 3))
@@ -317,11 +312,7 @@ __global__ __launch_bounds__(NT, 2) void cfconv_fwd_kernel(Params p) {
                     const u32x2 lo = *reinterpret_cast<const u32x2*>(buf + (2 * pc) * DCS + r * 8);
                     const u32x2 hi = *reinterpret_cast<const u32x2*>(buf + (2 * pc + 1) * DCS + r * 8);
                     if (r < nv) {
-#ifdef MDL_CF_SMALLDST
-                        unsigned* g = reinterpret_cast<unsigned*>(dst + (int64_t)((eb + r) & 4095) * F + u0);   // (A/B: stores that stay in L2)
-#else
                         unsigned* g = reinterpret_cast<unsigned*>(dst + (int64_t)(eb + r) * F + u0);
-#endif
                         if (b < NBK - 1 || ndw == 4) {
                             // (non-temporal stores measured: 522 -> 950 us — the 64-byte runs need the L2 to merge them into lines)
                             *reinterpret_cast<u32x4*>(g) = u32x4{lo[0], lo[1], hi[0], hi[1]};

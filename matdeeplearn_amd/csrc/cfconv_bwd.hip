@@ -22,10 +22,6 @@
 
 #include "mdl_common.h"
 
-// experiment builds only (tools/build_variant.sh): MDL_CFB_SKIP = bit mask of phases left out, for timing ablations (results are then wrong)
-#ifndef MDL_CFB_SKIP
-#define MDL_CFB_SKIP 0
-#endif
 
 namespace mdl {
 namespace cfb {
@@ -199,10 +195,6 @@ __global__ __launch_bounds__(NT, 2) void cfconv_bwd_w_kernel(Params p) {
         }
         cuc = vc;
         const int d0 = min(lane, FH - 1), d1 = min(tdw, FH - 1);
-        if (MDL_CFB_SKIP & 16) {            // (ablation: every row is node 0's)
-#pragma unroll
-            for (int r = 0; r < RPW; ++r) sn[r] = tn[r] = 0;
-        }
 #pragma unroll
         for (int r = 0; r < RPW; ++r) {
             h0[r] = reinterpret_cast<const unsigned*>(p.h + (int64_t)sn[r] * F)[d0];
@@ -252,7 +244,6 @@ __global__ __launch_bounds__(NT, 2) void cfconv_bwd_w_kernel(Params p) {
     // the fifth unit block of edge block eb is computed by all four waves of that parity (4 MFMAs: cheap) and each applies the
     // activation to a quarter of it
     auto s1 = [&](const bf16_t* et) {
-        if (MDL_CFB_SKIP & 1) return;
         auto ssp2 = [](float t0, float t1) { return pk_bf16(LN2_F * (GT::softplus_u(t0) - 1.0f), LN2_F * (GT::softplus_u(t1) - 1.0f)); };
         const int eb = wv & 1, ub = wv >> 1;
         if constexpr (NB == 5) {
@@ -300,8 +291,7 @@ __global__ __launch_bounds__(NT, 2) void cfconv_bwd_w_kernel(Params p) {
     };
     auto s2 = [&]() {
         // S2a: dW2 += dw^T . a1 (k = the tile's 64 edges)
-        if (MDL_CFB_SKIP & 2) { }
-        else if (cls2 == 0) tn_step<2, 2>(al, LA, r0, bl, LA, c0, i, h, acc);
+        if (cls2 == 0) tn_step<2, 2>(al, LA, r0, bl, LA, c0, i, h, acc);
         else if (cls2 == 1) tn_step<1, 4>(al, LA, r0, bl, LA, c0, i, h, acc);
         else if (cls2 == 2) tn_step<4, 1>(al, LA, r0, bl, LA, c0, i, h, acc);
         else if (cls2 == 3) tn_step<1, 1>(al, LA, r0, bl, LA, c0, i, h, acc);
@@ -310,7 +300,7 @@ __global__ __launch_bounds__(NT, 2) void cfconv_bwd_w_kernel(Params p) {
 #pragma unroll
         for (int bb = 0; bb < 2; ++bb) {
             const int bidx = wv + NW * bb;
-            if (bidx < 2 * NB && !(MDL_CFB_SKIP & 4)) {
+            if (bidx < 2 * NB) {
                 const int eb = bidx & 1, kb = bidx >> 1;
                 f32x16 d;
 #pragma unroll
@@ -336,7 +326,6 @@ __global__ __launch_bounds__(NT, 2) void cfconv_bwd_w_kernel(Params p) {
         }
     };
     auto s3 = [&](const bf16_t* et) {           // S3: dW1 += da^T . [rbf | 1]
-        if (MDL_CFB_SKIP & 8) return;
         if (NB >= 4 || b1a >= 0) tn_step<1, 1>(dl, LA, b1a >> 1, et, ES, b1a & 1, i, h, acc + 4);
         if (b1b >= 0) tn_step<1, 1>(dl, LA, b1b >> 1, et, ES, b1b & 1, i, h, acc + 3);
     };
@@ -385,7 +374,6 @@ __global__ __launch_bounds__(NT, 2) void cfconv_bwd_w_kernel(Params p) {
         __syncthreads();
     }
 
-    if (MDL_CFB_SKIP & 32) return;
     // ---- flush.  256 workgroups adding 35 blocks each into the same 33 k addresses with atomics cost 160 us of a 530-us launch
     // (all workgroups finish together): with a scratch buffer the blocks leave as plain coalesced stores in accumulator layout
     // (register r of a block: 64 consecutive floats) and cfconv_bwd_w_reduce_kernel sums them

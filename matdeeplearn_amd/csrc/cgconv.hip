@@ -30,7 +30,7 @@
 // because hipcc derives each s_waitcnt from the worst path into it: one path that skips the prefetches makes the waits
 // in front of the x-fragment MFMAs drain the loads issued a few instructions earlier.
 // cgconv_cb.inc (included below) holds a second, cooperative weight-stationary design of both kernels (opt-in).
-// DESIGN.md section 4 has the measured phase breakdown and the list of variants behind the MDL_* switches below.
+// DESIGN.md section 4 has the measured phase breakdown and the list of variants that were measured against this design.
 //
 // dtype MDL_BF16: v_mfma_f32_32x32x16_bf16, fast gate math.  MDL_F32 (parity mode):
 // v_mfma_f32_32x32x2_f32 (bit-exact fp32 fma chain), precise gate math.
@@ -53,14 +53,10 @@ namespace mdl {
 // form costs one v_accvgpr_read per value, 96 per tile), while the per-wave kernels of this unit, which live on 256 + 179
 // registers, need the AGPR form.
 namespace ep {
-#ifndef MDL_EP_DEFAULT
-#define MDL_EP_DEFAULT 2      // edge-per-lane backward edge pass for bf16, C = 64, G = 50: 2 = cgconv_ep2.inc where the by-source
-                              // sums are bf16 (mdl_cgconv_bwd_h): 6-9 % faster than the per-wave kernel on the bench batch; 0 = the
-                              // per-wave kernel always.  Callers override per launch with MDL_K3_PER_WAVE / MDL_K3_EDGE_LANE.
-#endif
-#ifndef MDL_EP2_MIN_EDGES
-#define MDL_EP2_MIN_EDGES 400000   // default selection of kernel 2: at least ~12 rounds per workgroup (MDL_K3_EDGE_LANE forces it)
-#endif
+constexpr int EP_DEFAULT = 2;         // edge-per-lane backward edge pass for bf16, C = 64, G = 50: 2 = cgconv_ep2.inc where the by-source
+                                      // sums are bf16 (mdl_cgconv_bwd_h): 6-9 % faster than the per-wave kernel on the bench batch; 0 = the
+                                      // per-wave kernel always.  Callers override per launch with MDL_K3_PER_WAVE / MDL_K3_EDGE_LANE.
+constexpr int64_t EP2_MIN_EDGES = 400000;   // default selection of kernel 2: at least ~12 rounds per workgroup (MDL_K3_EDGE_LANE forces it)
 #if MDL_EXPERIMENTS
 int launch(CgParams& p, hipStream_t st, int wgs, const char* name);      // experiments/csrc/cgconv_ep.inc: phases one after the other
 #endif
@@ -192,13 +188,16 @@ __global__ __launch_bounds__(256) void cgconv_pack_split_kernel(const float* __r
 // Host-side dispatch
 // ------------------------------------------------------------------------------------------
 static constexpr int LDS_CAP = 160 * 1024;
+constexpr int FWD_RANGE_EDGES = 64;    // edges per node range (= per wave) below which the launch shrinks instead: two 32-edge tiles
+constexpr int BWD_RANGE_EDGES = 128;   // (64 -> 128: -7 of 45 us at the reference's batch size — half as many waves flush their weight-gradient sums;
+                                       // from 6.5e4 edges on the grid is capped at one workgroup per CU either way)
 
 // Experiment switches.  libmdl_hip.so never reads the environment: variants a caller or a test wants are explicit flag bits
 // in the `dtype` argument (MDL_DETERMINISTIC, MDL_K3_PER_WAVE, MDL_K3_EDGE_LANE).  The experiments build (experiments/build.py,
 // -DMDL_EXPERIMENTS=1) reads them from the environment ONCE (first launch).
 struct CgEnv {
     int64_t grid_cap;     // MDL_GRID_CAP: upper bound on the grid (0 = none)
-    int cb_fwd, cb_bwd;   // MDL_CG_CB / MDL_CG_CB_BWD: cooperative column-block kernels (-1 = compile-time default)
+    int cb_fwd, cb_bwd;   // MDL_CG_CB / MDL_CG_CB_BWD: cooperative column-block kernels (1 = on; -1 = unset: off)
     int cb_wgs;           // MDL_CB_WGS: their workgroups per CU (0 = default)
     int ab_wgs;           // MDL_AB_WGS: workgroups per CU of the saved-gate backward (0 = default 1)
     int no_half_groups;   // MDL_CG_NO_HALF=1: dynamic backward schedule without the half-group tail (A/B)
@@ -269,8 +268,8 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
     // (r_src rows, dwe, db) then receives its terms from a single wave in program order, i.e. the same bits on every run.
     // For HIP-vs-HIP tests (graph replay vs eager, padded rows, data-parallel exchange); ~1/500 of the throughput.
     const bool det = bwd && (p.flags & MDL_DETERMINISTIC) != 0;
-    const int waves = det ? 1 : (bwd ? 4 : MDL_FWD_THREADS / 64);
-    // static fast shapes keep W in registers (no LDS copy); otherwise LDS if it fits, else global
+    const int waves = det ? 1 : (bwd ? 4 : FWD_THREADS / 64);
+    // W in LDS if it fits, else global
     const bool fast = !p.eperm && p.G == 50 && p.C == d.Cp && (d.Cp == 32 || d.Cp == 64) &&
                       (sizeof(T) == 2 ? (vec == 8 && EW == 2) : d.Cp == 64) &&
                       (bwd || (reinterpret_cast<uintptr_t>(p.out) % 16 == 0 && reinterpret_cast<uintptr_t>(p.x) % 16 == 0));
@@ -280,7 +279,7 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
                          p.bias_col && reinterpret_cast<uintptr_t>(p.x) % 16 == 0 &&
                          (bwd ? reinterpret_cast<uintptr_t>(p.gout) % 16 == 0 : reinterpret_cast<uintptr_t>(p.out) % 16 == 0) &&
                          !cg_env().no_fast128;
-    bool w_lds = (!fast || MDL_CG_WM != 2) && w_bytes + waves * p.wave_lds_bytes <= LDS_CAP;
+    bool w_lds = w_bytes + waves * p.wave_lds_bytes <= LDS_CAP;
     int lds = (w_lds ? w_bytes : 0) + waves * p.wave_lds_bytes;
     // packed weights that do not fit (C = 100 -> Cp = 128: 168 KB): every workgroup keeps the 64 rows of ONE channel slice
     p.w_slice = 0;
@@ -293,27 +292,27 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
     }
     const int wg_per_cu = lds * 2 <= LDS_CAP ? 2 : 1;
 
-    const bool all_slices = !bwd && fast && MDL_FWD_ALLSLICES && MDL_CG_WM == 1 && (sizeof(T) == 2 || w_lds);
+    const bool all_slices = !bwd && fast && (sizeof(T) == 2 || w_lds);
     // one node range per wave (per slice), at least ~2 edge tiles each; see NodeRange
-    const int64_t ranges = std::max<int64_t>(1, std::min<int64_t>(cdiv(p.E, bwd ? MDL_BWD_RANGE_EDGES : MDL_FWD_RANGE_EDGES), p.N));
+    const int64_t ranges = std::max<int64_t>(1, std::min<int64_t>(cdiv(p.E, bwd ? BWD_RANGE_EDGES : FWD_RANGE_EDGES), p.N));
     int64_t items = ranges * (all_slices ? 1 : d.NS);
     int64_t grid = cdiv(items, waves);
-    // backward is register-allocated for MDL_BWD_WAVES waves per SIMD: 1 -> one 4-wave workgroup per CU
-    const int64_t cap = 256 * ((bwd && MDL_BWD_WAVES == 1) ? 1 : wg_per_cu);
+    // backward is register-allocated for BWD_WAVES waves per SIMD: 1 -> one 4-wave workgroup per CU
+    const int64_t cap = 256 * ((bwd && BWD_WAVES == 1) ? 1 : wg_per_cu);
     if (grid > cap) grid = cap;
     const CgEnv& env = cg_env();
     if (env.grid_cap > 0 && grid > env.grid_cap) grid = env.grid_cap;   // experiments build
     if (det) { grid = d.NS; p.ctr = nullptr; }
     // edge-per-lane backward (cgconv_ep2.inc): bf16, C = 64, G = 50, target-sorted edge features, bf16 by-source sums
     if constexpr (sizeof(T) == 2) {
-        int ep_sel = env.ep >= 0 ? env.ep : MDL_EP_DEFAULT;
+        int ep_sel = env.ep >= 0 ? env.ep : ep::EP_DEFAULT;
         if (p.flags & MDL_K3_PER_WAVE) ep_sel = 0;
         const bool force2 = env.ep == 2 || (p.flags & MDL_K3_EDGE_LANE) != 0;
         if (force2) ep_sel = 2;
         if (ep_sel != 0 && !det && bwd && fast && !wsp && d.Cp == 64 && p.bias_col && p.E >= 64) {
             // (a workgroup of kernel 2 stages 51 KB of weights and clears 112 KB of tile buffers before its first tile: below a few
             // rounds per workgroup the per-wave kernel wins — 0.64 vs 0.71 ms per step at the reference's batch size 100)
-            if (ep_sel == 2 && p.rs16 && (force2 || p.E >= MDL_EP2_MIN_EDGES)) { g_last_k3 = 2; return ep::launch2(p, st, env.ep_wgs, name); }
+            if (ep_sel == 2 && p.rs16 && (force2 || p.E >= ep::EP2_MIN_EDGES)) { g_last_k3 = 2; return ep::launch2(p, st, env.ep_wgs, name); }
 #if MDL_EXPERIMENTS
             if (ep_sel == 1 && !p.rs16) return ep::launch(p, st, env.ep_wgs, name);      // fp32 by-source sums (mdl_cgconv_bwd)
 #endif
@@ -362,9 +361,9 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
 
     // cooperative column-block kernels (cgconv_cb.inc): bf16 static shapes
     if constexpr (sizeof(T) == 2) {
-        const bool use_cb = env.cb_fwd >= 0 ? env.cb_fwd != 0 : (MDL_CG_CB_DEFAULT != 0);
-        if (use_cb && fast && !wsp && !bwd && p.E >= 64 && p.bias_col) {   // (E >= 64: the kernels' edge-feature window is 1024 dwords)
-            const int cb_wgs = env.cb_wgs > 0 ? env.cb_wgs : MDL_CB_FWD_WG_PER_CU;
+        constexpr int CB_FWD_WG_PER_CU = 2;
+        if (env.cb_fwd > 0 && fast && !wsp && !bwd && p.E >= 64 && p.bias_col) {   // (E >= 64: the kernels' edge-feature window is 1024 dwords)
+            const int cb_wgs = env.cb_wgs > 0 ? env.cb_wgs : CB_FWD_WG_PER_CU;
             int64_t cb_grid = std::min<int64_t>(256 * cb_wgs, ranges);
             if (env.grid_cap > 0 && cb_grid > env.grid_cap) cb_grid = env.grid_cap;
             if (d.Cp == 64) {
@@ -376,8 +375,7 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
             }
             return check_launch(name);
         }
-        const bool use_cbb = env.cb_bwd >= 0 ? env.cb_bwd != 0 : (MDL_CG_CB_BWD_DEFAULT != 0);
-        if (use_cbb && fast && !wsp && !p.rs16 && bwd && p.E >= 64 && p.bias_col) {
+        if (env.cb_bwd > 0 && fast && !wsp && !p.rs16 && bwd && p.E >= 64 && p.bias_col) {
             const int cb_wgs = env.cb_wgs > 0 ? env.cb_wgs : MDL_CB_BWD_OCC;
             const int64_t cb_grid = std::min<int64_t>(256 * cb_wgs, ranges);
             if (d.Cp == 64) {
@@ -453,13 +451,13 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
 #endif
 #ifdef MDL_CG_FAST_ONLY   // compile-time experiments: only the bf16 C=64 G=50 instantiation
     if constexpr (sizeof(T) == 2) {
-        if (fast && d.Cp == 64) MDL_CG_LAUNCH(64, 50, 9, 2, MDL_CG_WM);
+        if (fast && d.Cp == 64) MDL_CG_LAUNCH(64, 50, 9, 2, 1);
         else if (fast128 && p.w_slice) MDL_CG_LAUNCH(128, 50, 9, 2, 1);
     }
 #else
     if constexpr (sizeof(T) == 2) {
-        if (fast && d.Cp == 64) MDL_CG_LAUNCH(64, 50, 9, 2, MDL_CG_WM);
-        else if (fast && d.Cp == 32) MDL_CG_LAUNCH(32, 50, 9, 2, MDL_CG_WM);
+        if (fast && d.Cp == 64) MDL_CG_LAUNCH(64, 50, 9, 2, 1);
+        else if (fast && d.Cp == 32) MDL_CG_LAUNCH(32, 50, 9, 2, 1);
         else if (fast128 && p.w_slice) MDL_CG_LAUNCH(128, 50, 9, 2, 1);
         else if (vec == 8) MDL_CG_BY_EW(8);
         else if (vec == 4) MDL_CG_BY_EW(4);
@@ -650,7 +648,7 @@ extern "C" int mdl_cgconv_fwd(const void* x, const void* edge_attr, const int32_
 }
 
 static int cg_fwd_stats_ok(int C, int G, int dtype) {      // the static all-slices forward: the kernel that has the epilogue
-    return (dtype == MDL_BF16 && G == 50 && (C == 32 || C == 64) && MDL_FWD_ALLSLICES && MDL_CG_WM == 1) ? 1 : 0;
+    return (dtype == MDL_BF16 && G == 50 && (C == 32 || C == 64)) ? 1 : 0;
 }
 
 extern "C" int mdl_cgconv_fwd_ex(const MdlCgConv* a, mdlStream_t stream) {

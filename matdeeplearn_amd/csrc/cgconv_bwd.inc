@@ -5,8 +5,9 @@ namespace mdl {
 // ------------------------------------------------------------------------------------------
 // Backward edge pass
 // ------------------------------------------------------------------------------------------
+constexpr int BWD_WAVES = 1;   // waves per SIMD the backward kernel is register-allocated for
 template <typename T, int CP_, int G_, int VEC, int EW, int WM, int WSP = 0, bool X3 = false>
-__global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams p) {
+__global__ __launch_bounds__(256, BWD_WAVES) void cgconv_bwd_kernel(CgParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef Mma<T> M;
     typedef Gate<M::FAST || X3> GT;   // x3: hardware exp2 / log2 / rcp (1 ulp) on base-2 pre-activations, like the bf16 kernels
@@ -15,7 +16,7 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
     constexpr bool BF = std::is_same<T, bf16_t>::value;
     const D dm(p);
     WaveCtx<T> w;
-    setup_wave<T>(p, dm, smem, WM == 1 || WM == 3, w);
+    setup_wave<T>(p, dm, smem, WM == 1, w);
     TDECL;
 
     const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
@@ -32,10 +33,6 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
     const T* x = static_cast<const T*>(p.x);
     const T* go = static_cast<const T*>(p.gout);
     const int C2 = 2 * dm.Cp;
-    constexpr int NKW = (WM == 2) ? (((G_ + 15) / 16 * 16) + 2 * CP_) / M::KSTEP : (WM == 3 ? 2 * CP_ / M::KSTEP : 1);
-    WRegs<T, NKW> wr;
-    if constexpr (WM == 2) wr.load(static_cast<const T*>(p.wpack), s * 32 + i, dm.Cp + s * 32 + i, dm.WS, h, 0);
-    if constexpr (WM == 3) wr.load(static_cast<const T*>(p.wpack), s * 32 + i, dm.Cp + s * 32 + i, dm.WS, h, dm.KE);
 
     // dwe accumulators: [part f|s][n-tile of G]  (rows = channel slot, cols = edge feature)
     constexpr int GNT = G_ ? (G_ + 31) / 32 : 2;
@@ -112,7 +109,7 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
         nxt = cur;
         if (e0 + 32 < e1) nxt.template load<!ST>(p, e0 + 32, e1, i, n0);
         nn = nxt;
-        constexpr bool XDB = MDL_BWD_XDB != 0 && !(X3 && CP_ > 64);   // (x3 at 128 channels: two sets of fp32 x chunks are 256 registers)
+        constexpr bool XDB = !(X3 && CP_ > 64);   // (x3 at 128 channels: two sets of fp32 x chunks are 256 registers)
         if constexpr (ST) ew.prefetch(p, lane, e0, min(32, e1 - e0), cur.ep);
         if constexpr (WSP != 0) pf.load(p.pt, p.ps, cur.tgt, cur.src, h, s);
         else if constexpr (CP_ != 0 && XDB) xf.load(x, dm.C, cur.tgt, cur.src, h);
@@ -202,7 +199,7 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
 #pragma unroll
             for (int r = 0; r < 16; ++r) { accf[r] = bf; accs[r] = bs; }
             if constexpr (WSP != 0) pre_tile_wsp<CP_, 1, 0>(dm, w, lane, s, 0, pf, idf, accf, accs);
-            else pre_tile<T, CP_, VEC, WM, NKW, 0, X3>(p, dm, w, lane, s, cur.tgt, cur.src, xf, wr, accf, accs);
+            else pre_tile<T, CP_, VEC, WM, 0, X3>(p, dm, w, lane, s, cur.tgt, cur.src, xf, accf, accs);
             TPIN16(accf); TPIN16(accs);
             TMARK(3);
 
@@ -237,11 +234,7 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     float sf, sp_u, ss;
-#if MDL_BWD_DERIV2
-                    if constexpr (BF) GT::deriv2(accf[r], accs[r], sf, sp_u, ss); else GT::deriv(accf[r], accs[r], sf, sp_u, ss);
-#else
                     GT::deriv(accf[r], accs[r], sf, sp_u, ss);
-#endif
                     const float t = dmv[r] * sf;
                     accf[r] = (t * GT::M_SCALE) * (1.0f - sf) * sp_u;
                     accs[r] = t * ss;
@@ -251,11 +244,7 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
             // sources outside the window: per-edge fp32 atomics (graphs wider than the window).  Issued as early as the
             // values exist: a pending atomic turns every later wait for a load into vmcnt(0) (loads and stores complete out of
             // order with respect to each other), so the more of this tile's MFMA work lies behind them the better
-#ifdef MDL_ABL_NOOOB
-            if (false) {
-#else
             if (__any(oob) && ch < dm.C) {
-#endif
                 // the 16 source ids of this lane's rows (d_row(4q+k, h) = 8q + 4h + k) in four 16-byte LDS reads up front:
                 // read one by one between the atomics, each costs an LDS round trip the compiler will not hoist
                 typedef __attribute__((ext_vector_type(4))) int i32x4;
@@ -296,10 +285,8 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
                 seg_reduce2_tab(dp, w.oh_t, i, h, Rf, Rs);                  // by target  -> r_tgt
                 TPIN16(Rf); TPIN16(Rs);
                 TMARK(7);
-#ifndef MDL_ABL_NOWIN
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) seg_reduce2_tab(dp, w.oh_w, i + 32 * mt, h, Wf[mt], Ws[mt]);   // by source window
-#endif
             } else {
                 unsigned t4[4], s4[4];
 #pragma unroll
@@ -318,9 +305,6 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
             TMARK(8);
             // dwe[ch][gcol] += sum_slot dpre[slot][ch] * e[slot][gcol]
             //   A = dpre^T (lane = channel, k = edge slots: own registers), B = e tile column (LDS)
-#ifdef MDL_ABL_NODWE
-            if (false)
-#endif
 #pragma unroll
             for (int nt = 0; nt < GNT; ++nt) {
                 const int gcol = nt * 32 + i;
@@ -393,9 +377,6 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
                      (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)tmv);
             }
             const unsigned long long tmh = tm >> (4 * h);
-#ifdef MDL_ABL_NOWFLUSH
-            if (p.N < 0)
-#endif
             if (BF && p.rs16) {
                 // (static bf16 shapes only: C == Cp, every lane owns a real column)
                 bf16_t* const b16 = reinterpret_cast<bf16_t*>(p.r_src) + (int64_t)(wb + 4 * h) * C2 + (ch & ~1);
@@ -448,9 +429,6 @@ __global__ __launch_bounds__(256, MDL_BWD_WAVES) void cgconv_bwd_kernel(CgParams
         }
     }
     // flush the wave's dwe partial sums: D rows = channel slot d_row(r,h) of slice s, cols = feature
-#ifdef MDL_ABL_NODWEFLUSH      // (timing experiments: wrong results)
-    if (p.N >= 0) return;
-#endif
     if (p.dwe_combine) {
         // Two slices, four waves: waves w and w + 2 of a workgroup hold partial sums of the SAME slice.  The flush is 64 atomic
         // instructions per wave on addresses every wave of the slice hits (12.5 of 45 us at the reference's batch size, where a

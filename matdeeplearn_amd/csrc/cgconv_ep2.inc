@@ -15,16 +15,6 @@
 
 namespace ep {
 
-#ifndef MDL_EP2_NWT
-#define MDL_EP2_NWT 4         // 32-row blocks of the by-source window
-#endif
-#ifndef MDL_EP2_TAIL
-#define MDL_EP2_TAIL 0        // per cent of the work (edges + nodes) handed out dynamically at the end (0: all static)
-#endif
-#ifndef MDL_EP2_WOFF
-#define MDL_EP2_WOFF 48       // rows of the window in front of the group's first node
-#endif
-
 template <int C_>
 struct Cfg2 {
     static constexpr int NB = 2 * C_ / 32;              // gate column blocks = reducer waves
@@ -34,8 +24,8 @@ struct Cfg2 {
     static constexpr int KT = KE + 2 * C_;
     static constexpr int WS = KT + 8;
     static constexpr int NKX = C_ / 16;
-    static constexpr int NWT = MDL_EP2_NWT;
-    static constexpr int WOFF = MDL_EP2_WOFF;
+    static constexpr int NWT = 4;                       // 32-row blocks of the by-source window
+    static constexpr int WOFF = 48;                     // rows of the window in front of the group's first node
     static constexpr int NCH = 2 * C_ / 4;
     static constexpr int DCS = 32 * 8 + 32;
     static constexpr int W_BYTES = 2 * C_ * WS * 2;
@@ -52,24 +42,13 @@ struct Cfg2 {
     static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
-#ifndef MDL_EP2_RNEXT
-#define MDL_EP2_RNEXT 1       // 1: the reducers learn from the tile headers whether another round follows (no walk of their own)
-#endif
-#ifndef MDL_EP2_FLUSHFAST
-#define MDL_EP2_FLUSHFAST 1   // 1: the two flushes of a full group / an inside window block store without per-row guards
-#endif
-#ifndef MDL_EP2_OHK
-#define MDL_EP2_OHK 1         // 1: one-hot operands in TWO packed instructions per pair (value 2^-126, see oh2x)
-#endif
-
-// one dword (two bf16 one-hot values) for two consecutive k-slots whose row ids are the halfwords of D: 1.0 where the halfword
-// equals the row id replicated in rsplat — xor, saturating 1 - x, times 0x3F80: three packed 16-bit instructions per pair.
-// MDL_EP2_OHK: the slots travel shifted left by 7 (the exponent field of a bf16), so the xor of two different slots is >= 0x0080
-// and ONE saturating 0x0080 - x leaves 0x0080 (= 2^-126, the smallest normal bf16) where they are equal and 0 elsewhere: two
-// instructions per pair.  The products stay normal fp32 numbers because the producers scale dpre by 2^OHK_S on the way into the
-// tile (folded into the 1 / deg factor: no instruction); the flushes divide it out (folded into their scale factor).
+// one dword (two bf16 one-hot values) for two consecutive k-slots whose row ids are the halfwords of D, nonzero where the
+// halfword equals the row id replicated in rsplat.  The slots travel shifted left by 7 (the exponent field of a bf16), so the
+// xor of two different slots is >= 0x0080 and ONE saturating 0x0080 - x leaves 0x0080 (= 2^-126, the smallest normal bf16)
+// where they are equal and 0 elsewhere: two packed 16-bit instructions per pair.  The products stay normal fp32 numbers
+// because the producers scale dpre by 2^64 on the way into the tile (folded into the 1 / deg factor: no instruction); the
+// flushes divide it out (folded into their scale factor).
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-#if MDL_EP2_OHK
 constexpr int OHK_SH = 7;
 constexpr float OHK_UP = 18446744073709551616.0f;            // 2^64: what the producers multiply dpre by
 constexpr float OHK_DOWN = 1.0f / 18446744073709551616.0f;   // 2^-64: the dwe sums and the out-of-window atomics
@@ -78,15 +57,6 @@ __device__ __forceinline__ unsigned oh2x(unsigned x) {
     const u16x2 k = {0x0080, 0x0080};
     return __builtin_bit_cast(unsigned, (u16x2)__builtin_elementwise_sub_sat(k, __builtin_bit_cast(u16x2, x)));
 }
-#else
-constexpr int OHK_SH = 0;
-constexpr float OHK_UP = 1.0f, OHK_DOWN = 1.0f, OHK_RW = 1.0f;
-__device__ __forceinline__ unsigned oh2x(unsigned x) {
-    const u16x2 one = {1, 1}, c = {0x3F80, 0x3F80};
-    const u16x2 y = __builtin_elementwise_sub_sat(one, __builtin_bit_cast(u16x2, x));
-    return __builtin_bit_cast(unsigned, (u16x2)(y * c));
-}
-#endif
 
 template <int C_>
 __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
@@ -113,8 +83,7 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
     }
     const bf16_t* const wl = reinterpret_cast<const bf16_t*>(smem);
 
-    // ---- work distribution: a static, cost-balanced node range per workgroup over the first (100 - MDL_EP2_TAIL) % of the
-    // work, the rest in chunks of MDL_EP2_DG groups from a counter (Walk; needs the caller's workspace, else all static)
+    // ---- work distribution: a static, cost-balanced node range per workgroup (Walk)
     Walk wk;
     {
         const int N = (int)p.N;
@@ -123,37 +92,15 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
         auto cost_at = [&](int n) -> int64_t { return key ? (int64_t)key[n] : (int64_t)p.rowptr[n] + n; };
         auto bound = [&](int64_t b) { return key ? wave_lower_bound_key(key, N, b, lane) : wave_lower_bound(p.rowptr, N, b, lane); };
         const int64_t Et = cost_at(N);
-        int ns = N;
-        if (p.ctr && MDL_EP2_TAIL > 0) {
-            ns = bound(Et * (100 - MDL_EP2_TAIL) / 100) & ~31;
-            if (ns < 32 * (int)gridDim.x) ns = N;                                 // (too small to split: all static)
-        }
-        const int64_t Es = cost_at(ns);
         const int W = (int)gridDim.x, wi = (int)blockIdx.x;
-        const int na = (wi == 0) ? 0 : min(bound(Es * wi / W), ns);
-        const int nb = (wi == W - 1) ? ns : min(bound(Es * (wi + 1) / W), ns);
-        if (ns < N) {
-            int* const q = reinterpret_cast<int*>(smem + F::W_BYTES + F::OFF_META) + 4;   // two spare header words of tile buffer 0
-            wk.init_dyn(p, na, nb, ns, q, p.ctr, wv == 0);
-            if (wv == 0) { wk.request(p); wk.publish(); }                         // the id of segment 1
-        } else {
-            wk.init(p, na, nb);
-        }
+        const int na = (wi == 0) ? 0 : min(bound(Et * wi / W), N);
+        const int nb = (wi == W - 1) ? N : min(bound(Et * (wi + 1) / W), N);
+        wk.init(p, na, nb);
     }
     __syncthreads();
-    // (the three tile-ahead calls below may cross a segment boundary on a tiny problem: a barrier behind each, like in the loop)
-    auto sync_walk = [&]() {
-        if (wk.ctr) {
-            if (wv == 0) wk.publish();
-            lds_barrier();
-        }
-    };
 
     if (wv < NA) {
         // ======================================= producer waves: phase A =======================================
-#if defined(MDL_EP2_PRIO_PROD)
-        __builtin_amdgcn_s_setprio(MDL_EP2_PRIO_PROD);      // (A/B: static priority for one role, no per-segment flips)
-#endif
         const int gw = blockIdx.x * NA + wv;
         (void)gw;
         TDECL;
@@ -174,11 +121,8 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
         }
         bool rh0, rh1, rh2, rh3;
         Tile m0 = take<NA>(p, wk, wv, rh0);
-        sync_walk();
         Tile m1 = take<NA>(p, wk, wv, rh1);
-        sync_walk();
         Tile m2 = take<NA>(p, wk, wv, rh2);
-        sync_walk();
         Tile m3 = m2;
         rh3 = rh2;
         Idx id0, id1, id2;
@@ -228,11 +172,6 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
                     TMARK(1);
                     id2.load(p, m2, i);
                     ew.prefetch(p, lane, m1.eb, 32, 0);
-#if defined(MDL_EP2_STAGGER)
-                    // (A/B: the four producers leave the barrier together, so their weight-fragment bursts — 48 KB per tile each, the
-                    // LDS pipe at full rate — coincide and the reducers' reads queue behind them; half of them start later)
-                    if (wv & MDL_EP2_STAGGER_MASK) __builtin_amdgcn_s_sleep(MDL_EP2_STAGGER);
-#endif
                     TMARK(2);
 
                     f32x16 acc[NB], dmv[HB];
@@ -252,20 +191,6 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
                                 const int b = bc + HB * u;
                                 acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ld_frag(wl, 32 * b + i, F::WS, 16 * k, h), zf[k], acc[b], 0, 0, 0);
                             }
-#ifdef MDL_EP2_ABL_WSPLIT_BOUND
-                        // timing bound of a W-split INSIDE the producers (wrong results): the x parts of the product become
-                        // identity-operand MFMAs on gathered rows (the x rows stand in for projection rows: half the gather volume
-                        // of the real thing) — 8 instead of 16 MFMAs per pair and a third of the weight-fragment reads.
-                        // Measured (round 4): 485.7 -> 475.6 us; the producers finish earlier and wait longer at the barrier.
-#pragma unroll
-                        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                            for (int u = 0; u < 2; ++u) {
-                                const int b = bc + HB * u;
-                                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(idf[ks], ga.t[2 * u + ks], acc[b], 0, 0, 0);
-                                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(idf[ks], ga.s[2 * u + ks], acc[b], 0, 0, 0);
-                            }
-#else
 #pragma unroll
                         for (int f = 0; f < F::NKX; ++f)
 #pragma unroll
@@ -280,7 +205,6 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
                                 const int b = bc + HB * u;
                                 acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ld_frag(wl, 32 * b + i, F::WS, F::KE + C_ + 16 * f, h), ga.s[f], acc[b], 0, 0, 0);
                             }
-#endif
 #pragma unroll
                         for (int ks = 0; ks < 2; ++ks)
                             dmv[bc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(idf[ks], ga.g[bc][ks], dmv[bc], 0, 0, 0);
@@ -304,17 +228,11 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
                             }
                         }
                     };
-#ifdef MDL_EP2_ABL_NOA
-                    if (p.N < 0)
-#endif
 #pragma unroll
                     for (int bc = 0; bc < HB; ++bc) {
                         mfma_pair(bc);
                         if (bc == HB - 1) ga.load(p, id1, h);      // the gathers of my next tile reuse the consumed fragment registers
                         gate_pair(bc);
-#ifdef MDL_EP2_ABL_NOOOW
-                        if (p.N < 0)
-#endif
                         if (any_oob) {
                             // registers 4q .. 4q+3 of block b = columns 32 b + 8 q + 4 h + (0..3) of this lane's edge: two
                             // packed pairs per quad; the f blocks carry the ln2 the reducers apply to everything else
@@ -342,13 +260,10 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
                 }
             }
             TMARK(3);
-            if (wv == 0) wk.publish();                     // (dynamic tail: the chunk id requested when this segment started)
-#if MDL_EP2_RNEXT
-            // the reducers do not walk the tile sequence any more (four Walk::next per round, 630 cycles of their critical path):
+            // the reducers do not walk the tile sequence (four Walk::next per round, 630 cycles of their critical path):
             // whether round t + 1 exists travels in the header of tile 0 of the set they reduce in round t + 1
             if (have && wv == 0 && lane == 0)
                 reinterpret_cast<int*>(smem + F::W_BYTES + ((t & 1) * NA) * F::BUF + F::OFF_META)[6] = rh1 ? 1 : 0;
-#endif
             lds_barrier();
             TMARK(4);
             TTILE();
@@ -361,9 +276,6 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
     }
 
     // ========================================= reducer waves: phase B =========================================
-#if defined(MDL_EP2_PRIO_RED)
-    __builtin_amdgcn_s_setprio(MDL_EP2_PRIO_RED);
-#endif
     const int cb = wv - NA;                              // gate column block [32 cb, 32 cb + 32)
     const int gw = (blockIdx.x == 0 && cb == 0) ? 0 : 1000000;   // (timing builds: reducer 0 of workgroup 0 reports)
     (void)gw;
@@ -386,14 +298,10 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
     // instruction: no 64-bit address arithmetic per row).  The accumulators were last written by MFMAs inside an asm
     // statement: the wait states for the reads are spelled out.
     auto flush_r = [&]() {
-#if defined(MDL_EP2_ABL_NOFLUSH) || defined(MDL_EP2_ABL_NOFLUSH_R)
-        if (p.N >= 0) return;
-#endif
         asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(Racc));
         const gbytes_t rt = (gbytes_t)p.r_tgt;
         const unsigned off0 = ((unsigned)(cn0 + 4 * h + odd) * C2 + (unsigned)(col & ~1)) * 2u;
         const int nrow = cn1 - cn0 - 4 * h - odd;
-#if MDL_EP2_FLUSHFAST
         if (cn1 - cn0 == 32) {                            // a full group (all but a workgroup's last): no per-row guards
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
@@ -405,7 +313,6 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
             }
             return;
         }
-#endif
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
             const float va = Racc[r] * fscale, vb = Racc[r + 1] * fscale;
@@ -418,9 +325,6 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
     };
     // by-source sums of one 32-row block in bf16 (packed atomics); rows past the last node are skipped
     auto flush_w = [&](f32x16& W, int row0) {
-#if defined(MDL_EP2_ABL_NOFLUSH) || defined(MDL_EP2_ABL_NOFLUSH_W)
-        if (p.N >= 0) return;
-#endif
         asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(W));
         typedef __bf16 __attribute__((ext_vector_type(2))) bf2v;
         typedef __attribute__((address_space(1))) bf2v* gptr_t;
@@ -428,7 +332,6 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
         const int grow0 = row0 + 4 * h + odd;
         const unsigned off0 = ((unsigned)grow0 * C2 + (unsigned)(col & ~1)) * 2u;
         const int nleft = p.N - grow0;
-#if MDL_EP2_FLUSHFAST
         if (row0 + 32 <= (int)p.N) {                      // the block lies inside the node array: no per-row guards
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
@@ -440,7 +343,6 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
             }
             return;
         }
-#endif
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
             const float va = W[r] * fscale, vb = W[r + 1] * fscale;
@@ -531,34 +433,12 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
         // first one's result, and the 12 packed instructions of a fragment cover its 32 cycles)
         unsigned xs[2][4];
         const bf16x8 d0 = dpf[0], d1 = dpf[1];
-#if defined(MDL_EP2_EBF_TOP)
-        // (A/B: the e-tile fragments requested in front of the by-target product instead of behind it)
-        bf16x8 ebf[2][2];
-        {
-            const bf16_t* const etj = reinterpret_cast<const bf16_t*>(bj + F::OFF_ET);
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const bf16_t* base = etj + (16 * ks + 4 * h + (t16 >> 2)) * F::EKS + nt * 32 + (i & 16) + 4 * (t16 & 3);
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)(base));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)(base + 8 * F::EKS));
-                    ebf[nt][ks] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                }
-        }
-#endif
         {
             const u32x2 t0 = tq[0][0], t1 = tq[0][1];
-            bf16x8 tf0 = __builtin_bit_cast(bf16x8, u32x4{oh2x(t0[0] ^ rsplat), oh2x(t0[1] ^ rsplat), oh2x(t1[0] ^ rsplat), oh2x(t1[1] ^ rsplat)});
-#ifdef MDL_EP2_ABL_NOOH
-            tf0 = d0;
-#endif
+            const bf16x8 tf0 = __builtin_bit_cast(bf16x8, u32x4{oh2x(t0[0] ^ rsplat), oh2x(t0[1] ^ rsplat), oh2x(t1[0] ^ rsplat), oh2x(t1[1] ^ rsplat)});
             asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %[R], %[t0], %[d0], %[R]" : [R] "+v"(Racc) : [t0] "v"(tf0), [d0] "v"(d0));
             const u32x2 u0 = tq[1][0], u1 = tq[1][1];
-            bf16x8 tf1 = __builtin_bit_cast(bf16x8, u32x4{oh2x(u0[0] ^ rsplat), oh2x(u0[1] ^ rsplat), oh2x(u1[0] ^ rsplat), oh2x(u1[1] ^ rsplat)});
-#ifdef MDL_EP2_ABL_NOOH
-            tf1 = d0;
-#endif
+            const bf16x8 tf1 = __builtin_bit_cast(bf16x8, u32x4{oh2x(u0[0] ^ rsplat), oh2x(u0[1] ^ rsplat), oh2x(u1[0] ^ rsplat), oh2x(u1[1] ^ rsplat)});
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const u32x2 s0 = sq[ks][0], s1 = sq[ks][1];
@@ -568,7 +448,6 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
         }
         TMARK(2);
         // the e-tile fragments of this tile and the operands of the next one travel while the window blocks are worked on
-#if !defined(MDL_EP2_EBF_TOP)
         bf16x8 ebf[2][2];
         {
             const bf16_t* const etj = reinterpret_cast<const bf16_t*>(bj + F::OFF_ET);
@@ -582,23 +461,14 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
                     ebf[nt][ks] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 }
         }
-#endif
-#ifndef MDL_EP2_NOPREFETCH
         request(bnext);
-#endif
 #pragma unroll
         for (int mt = 0; mt < NWT; ++mt) {
             if (touched & (1u << mt)) {
                 const unsigned m = (unsigned)((32 * mt) << OHK_SH) * 0x00010001u;      // row 32 mt + i = i | 32 mt: the xor splits
-                bf16x8 w0 = __builtin_bit_cast(bf16x8, u32x4{oh2x(xs[0][0] ^ m), oh2x(xs[0][1] ^ m), oh2x(xs[0][2] ^ m), oh2x(xs[0][3] ^ m)});
-#ifdef MDL_EP2_ABL_NOOH
-                w0 = d1;
-#endif
+                const bf16x8 w0 = __builtin_bit_cast(bf16x8, u32x4{oh2x(xs[0][0] ^ m), oh2x(xs[0][1] ^ m), oh2x(xs[0][2] ^ m), oh2x(xs[0][3] ^ m)});
                 asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %[W], %[w0], %[d0], %[W]" : [W] "+v"(Wacc[mt]) : [w0] "v"(w0), [d0] "v"(d0));
-                bf16x8 w1 = __builtin_bit_cast(bf16x8, u32x4{oh2x(xs[1][0] ^ m), oh2x(xs[1][1] ^ m), oh2x(xs[1][2] ^ m), oh2x(xs[1][3] ^ m)});
-#ifdef MDL_EP2_ABL_NOOH
-                w1 = d1;
-#endif
+                const bf16x8 w1 = __builtin_bit_cast(bf16x8, u32x4{oh2x(xs[1][0] ^ m), oh2x(xs[1][1] ^ m), oh2x(xs[1][2] ^ m), oh2x(xs[1][3] ^ m)});
                 asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %[W], %[w1], %[d1], %[W]\n\ts_nop 3" : [W] "+v"(Wacc[mt]) : [w1] "v"(w1), [d1] "v"(d1));
             }
         }
@@ -611,63 +481,39 @@ __global__ __launch_bounds__(Cfg2<C_>::NT, 2) void bwd2_kernel(CgParams p) {
             "s_nop 7"
             : [E0] "+v"(dwe[0]), [E1] "+v"(dwe[1])
             : [d0] "v"(d0), [d1] "v"(d1), [e00] "v"(ebf[0][0]), [e01] "v"(ebf[0][1]), [e10] "v"(ebf[1][0]), [e11] "v"(ebf[1][1]));
-#ifdef MDL_EP2_NOPREFETCH
-        request(bnext);
-#endif
         TMARK(4);
     };
 
     {
-        // the reducers walk the same tile sequence (scalar work only) to know how many rounds there are
-        bool rh0, rh1, rh2, rh3;
+        // the reducers take the first rounds of the tile sequence like the producers (scalar work only): whether round 0 exists
+        bool rh0, rh1, rh2;
         (void)take<NA>(p, wk, 0, rh0);
-        sync_walk();
         (void)take<NA>(p, wk, 0, rh1);
-        sync_walk();
         (void)take<NA>(p, wk, 0, rh2);
-        sync_walk();
-        rh3 = rh2;
+        bool have = rh0;                                  // (later rounds: from the header, below)
         for (int t = 0;; ++t) {
-#if MDL_EP2_RNEXT
-            bool have = rh0;                              // (t == 0; later rounds: from the header, below)
-#else
-            const bool have = rh0;
-            if (have) (void)take<NA>(p, wk, 0, rh3);
-#endif
             if (t > 0) {
                 const char* set = smem + F::W_BYTES + (((t - 1) & 1) * NA) * F::BUF;
-#if MDL_EP2_RNEXT
                 have = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(set + F::OFF_META)[6]) != 0;
-#endif
-#ifdef MDL_EP2_ABL_NOB
-                if (p.N < 0)
-#endif
-                {
-                    // the headers of the round's four tiles in one read: lane j holds tile j's
-                    TMARK(11);
-                    const i32x4 hd = *reinterpret_cast<const i32x4*>(set + (lane & (NA - 1)) * F::BUF + F::OFF_META);
-                    request(set);
-                    TMARK(12);
-#if defined(MDL_EP2_UNROLLJ)
-#pragma unroll
-#else
+                // the headers of the round's four tiles in one read: lane j holds tile j's
+                TMARK(11);
+                const i32x4 hd = *reinterpret_cast<const i32x4*>(set + (lane & (NA - 1)) * F::BUF + F::OFF_META);
+                request(set);
+                TMARK(12);
 #pragma unroll 1
-#endif
-                    // (the last tile of a round requests operands too — tile 0 of the set again, unused: with ONE code path the wait
-                    // in front of the dwe product counts the requests in flight (lgkmcnt(8)) instead of draining them (lgkmcnt(0)
-                    // at the join of the two paths): K3 483 -> 476 us)
-                    for (int j = 0; j < NA; ++j)
-                        tile_step(set + j * F::BUF, __builtin_amdgcn_readlane(hd[0], j), __builtin_amdgcn_readlane(hd[1], j),
-                                  __builtin_amdgcn_readlane(hd[2], j), (unsigned)__builtin_amdgcn_readlane(hd[3], j),
-                                  set + ((j + 1) & (NA - 1)) * F::BUF);
-                }
+                // (the last tile of a round requests operands too — tile 0 of the set again, unused: with ONE code path the wait
+                // in front of the dwe product counts the requests in flight (lgkmcnt(8)) instead of draining them (lgkmcnt(0)
+                // at the join of the two paths): K3 483 -> 476 us)
+                for (int j = 0; j < NA; ++j)
+                    tile_step(set + j * F::BUF, __builtin_amdgcn_readlane(hd[0], j), __builtin_amdgcn_readlane(hd[1], j),
+                              __builtin_amdgcn_readlane(hd[2], j), (unsigned)__builtin_amdgcn_readlane(hd[3], j),
+                              set + ((j + 1) & (NA - 1)) * F::BUF);
             }
             TMARK(5);
             lds_barrier();
             TMARK(6);
             TTILE();
             if (!have) break;
-            rh0 = rh1; rh1 = rh2; rh2 = rh3;
         }
     }
     if (cn0 >= 0) {

@@ -12,9 +12,6 @@ typedef __attribute__((address_space(3))) s16x4* lds4_t;
 // LDS-only workgroup barrier: the fences name the local address space, so no vmcnt wait is attached to it and the global
 // loads prefetched for the next round stay in flight across it.
 __device__ __forceinline__ void lds_barrier() {
-#ifdef MDL_EP_ABL_NOBAR
-    return;
-#endif
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
@@ -27,33 +24,10 @@ __device__ __forceinline__ void lds_barrier() {
 // every LDS access, so the next LDS wait of the wave also waited for it (a memory round trip per group: 2-5 % of the kernel on
 // the bench batch, and the whole kernel time again on the run of edge-less padding nodes at the end of a static batch, where
 // every tile is a group change).
-#ifndef MDL_EP2_FINE
-#define MDL_EP2_FINE 40         // per cent of the dynamic tail handed out in single groups (its end)
-#endif
-#ifndef MDL_EP2_DG
-#define MDL_EP2_DG 2            // groups per chunk of the dynamic tail (kernel 2)
-#endif
 struct Walk {
     int n0, n1, e0, e1, eb, nb, used;
     int ends;            // lane 0: rowptr[nbase]; lane k: rowptr[min(nbase + 32 k, nb)] = end of the (k-1)-th group from node nbase
     bool done;           // no tile left
-    // ---- dynamic tail (kernel 2 with a caller workspace): after its static range a workgroup takes chunks of MDL_EP2_DG
-    // groups of the LAST part of the node array from a global counter.  Equal tile counts are not equal time (a workgroup
-    // that holds large graphs touches more window blocks and has more out-of-window tiles: measured end times 431 / 458 /
-    // 523 us min / median / max at equal round counts), and the kernel ends with its slowest workgroup.  All eight waves of a
-    // workgroup walk the same tile sequence, so the chunk ids travel through a two-entry LDS queue: the fetching wave
-    // requests the id of segment k + 1 when segment k starts and publishes it before that round's barrier; a segment always
-    // ends its round (the remaining tile slots stay empty), so every reader is at least one barrier behind the writer.
-    bool seg_end;        // the segment ended in this round
-    bool fetcher;        // this wave feeds the queue
-    bool pend_valid;
-    int dyn_n0, dyn_nc;  // first node of the dynamic region, chunks in it
-    int dyn_nc1;         // how many of them are MDL_EP2_DG groups long (the later ones: one group)
-    int seg;             // segments started
-    int pend;            // lane 0 of the fetcher: chunk id in flight
-    int nodes;           // p.N
-    int* q;              // LDS: q[k & 1] = chunk id of segment k (k >= 1), -1 = none left
-    unsigned* ctr;       // null: static range only
     __device__ __forceinline__ void fetch(const CgParams& p, int nbase) {
         const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
         const int32_t* a = p.rowptr + min(nbase + 32 * lane, nb);
@@ -71,52 +45,16 @@ struct Walk {
         eb = e0;
     }
     __device__ __forceinline__ void init(const CgParams& p, int na, int nb_) {
-        ends = 0; ctr = nullptr; q = nullptr; seg_end = false; fetcher = false; pend_valid = false; dyn_n0 = dyn_nc = dyn_nc1 = seg = pend = 0;
-        nodes = (int)p.N;
+        ends = 0;
         start(p, na, nb_);
         done = na >= nb_;
-    }
-    // static range [na, nb_) first, then chunks of the region that starts at node dn0 (nc of them)
-    __device__ __forceinline__ void init_dyn(const CgParams& p, int na, int nb_, int dn0, int* q_, unsigned* ctr_, bool fetcher_) {
-        init(p, na, nb_);
-        ctr = ctr_; q = q_; fetcher = fetcher_; dyn_n0 = dn0;
-        const int groups = (nodes - dn0 + 31) / 32;                       // groups of the dynamic region
-        dyn_nc1 = groups * (100 - MDL_EP2_FINE) / 100 / MDL_EP2_DG;
-        dyn_nc = dyn_nc1 + (groups - dyn_nc1 * MDL_EP2_DG);
-        done = false;
-        seg_end = na >= nb_;                               // (an empty static range: straight to the queue)
-    }
-    __device__ __forceinline__ void request(const CgParams& p) {
-        const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        if (lane == 0) pend = (int)atomicAdd(ctr, 1u);
-        pend_valid = true;
-    }
-    // (fetcher, before the barrier that ends the round) the id requested when the current segment started
-    __device__ __forceinline__ void publish() {
-        if (!pend_valid) return;
-        const int c = __builtin_amdgcn_readfirstlane(pend);
-        q[(seg + 1) & 1] = c < dyn_nc ? c : -1;
-        pend_valid = false;
-    }
-    __device__ __forceinline__ void advance(const CgParams& p) {
-        seg_end = false;
-        ++seg;
-        const int c = __builtin_amdgcn_readfirstlane(q[seg & 1]);
-        if (c < 0) { done = true; return; }
-        // the first dyn_nc1 chunks hold MDL_EP2_DG groups, the rest ONE: the counter runs out while every workgroup still owns
-        // its current and its announced chunk, so the kernel's tail is two chunks long — they had better be small ones
-        int a, len;
-        if (c < dyn_nc1) { a = dyn_n0 + c * (32 * MDL_EP2_DG); len = 32 * MDL_EP2_DG; }
-        else { a = dyn_n0 + dyn_nc1 * (32 * MDL_EP2_DG) + (c - dyn_nc1) * 32; len = 32; }
-        start(p, a, min(a + len, nodes));
-        if (fetcher) request(p);
     }
     __device__ __forceinline__ bool last() const { return eb + 32 >= e1; }
     __device__ __forceinline__ void next(const CgParams& p) {
         if (!last()) { eb += 32; return; }
         n0 = n1;
         if (n0 >= nb) {
-            if (ctr) seg_end = true; else done = true;
+            done = true;
             return;
         }
         if (used == 64) { fetch(p, n0); used = 1; }       // (once per 63 groups)
@@ -137,12 +75,11 @@ struct Tile {          // wave-uniform snapshot of the walker
 // the tile of wave `wv` in the next round; every wave walks all NW tiles so that all agree on the sequence
 template <int NW>
 __device__ __forceinline__ Tile take(const CgParams& p, Walk& wk, int wv, bool& round_has) {
-    if (wk.seg_end) wk.advance(p);                        // a new segment starts with a round
     Tile m = {wk.n0, wk.n1, wk.e1, wk.eb, false};
     round_has = !wk.done;
 #pragma unroll
     for (int j = 0; j < NW; ++j) {
-        const bool live = !wk.done && !wk.seg_end;
+        const bool live = !wk.done;
         if (j == wv) m = Tile{wk.n0, wk.n1, wk.e1, wk.eb, live};
         if (live) wk.next(p);
     }
@@ -164,9 +101,6 @@ struct Gathers {
     bf16x8 t[C_ / 16], s[C_ / 16], g[C_ / 32][2];
     int rp0, rp1;
     __device__ __forceinline__ void load(const CgParams& p, const Idx& id, int h) {
-#ifdef MDL_EP_ABL_NOGATHER
-        if (p.N >= 0) { rp0 = id.tgt; rp1 = id.src; return; }
-#endif
         const bf16_t* xt = static_cast<const bf16_t*>(p.x) + (int64_t)id.tgt * C_ + 8 * h;
         const bf16_t* xs = static_cast<const bf16_t*>(p.x) + (int64_t)id.src * C_ + 8 * h;
         const bf16_t* gt = static_cast<const bf16_t*>(p.gout) + (int64_t)id.tgt * C_ + 8 * h;

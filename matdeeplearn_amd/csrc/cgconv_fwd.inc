@@ -2,19 +2,17 @@
 // Included by cgconv.hip behind cgconv_tiles.inc.
 namespace mdl {
 
-#ifndef MDL_FWD_THREADS
-#define MDL_FWD_THREADS 256     // workgroup size of the forward kernel (waves share one LDS copy of W)
-#define MDL_FWD_WAVES 2         // waves per SIMD it is register-allocated for
-#endif
-// BN_: the instantiation whose epilogue also forms the BatchNorm statistics of the output (p.bn_sums) — a variant of its own, so
-// that the plain forward keeps its register allocation (it sits at 252 of 256 VGPRs)
-template <typename T, int CP_, int G_, int VEC, int EW, int WM, bool AB_ = false, int WSP = 0, bool BN_ = false, bool X3 = false>   // WM: 0 global, 1 LDS, 2 registers; X3: split-bf16 products on fp32 storage
+constexpr int FWD_THREADS = 256;   // workgroup size of the forward kernel (waves share one LDS copy of W)
+constexpr int FWD_WAVES = 2;       // waves per SIMD it is register-allocated for
 // (fp32: the packed weights alone are 99 KB of LDS, so one 4-wave workgroup fits a CU whatever the register count — the fp32
 // STATIC instantiation is allocated for ONE wave per SIMD (512 registers) instead of spilling 102 registers at 256: round 6)
-#ifndef MDL_FWD_WAVES_F32
-#define MDL_FWD_WAVES_F32 1
-#endif
-__global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MDL_FWD_WAVES_F32 : MDL_FWD_WAVES)) void cgconv_fwd_kernel(CgParams p) {
+constexpr int FWD_WAVES_F32 = 1;
+constexpr int FWD_PRE_DEPTH = 3;   // all-slices forward: pinned LDS-read / MFMA interleave in pre_tile, reads issued ahead (-6 %)
+constexpr int FWD_AGE_SKEW = 60;   // all-slices forward at two workgroups per CU: per mille of extra work for the older half
+// BN_: the instantiation whose epilogue also forms the BatchNorm statistics of the output (p.bn_sums) — a variant of its own, so
+// that the plain forward keeps its register allocation (it sits at 252 of 256 VGPRs)
+template <typename T, int CP_, int G_, int VEC, int EW, int WM, bool AB_ = false, int WSP = 0, bool BN_ = false, bool X3 = false>   // WM: 0 global, 1 LDS; X3: split-bf16 products on fp32 storage
+__global__ __launch_bounds__(FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? FWD_WAVES_F32 : FWD_WAVES)) void cgconv_fwd_kernel(CgParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef Mma<T> M;
     typedef Gate<M::FAST || X3> GT;   // x3: hardware exp2 / log2 / rcp (1 ulp) on base-2 pre-activations, like the bf16 kernels
@@ -22,7 +20,7 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
     constexpr bool ST = D::STATIC;
     const D dm(p);
     WaveCtx<T> w;
-    setup_wave<T>(p, dm, smem, WM == 1 || WM == 3, w);
+    setup_wave<T>(p, dm, smem, WM == 1, w);
     TDECL;
 
     const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
@@ -39,13 +37,8 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
     const float bs = (BC || p.bias_col) ? 0.0f : p.bpack[dm.Cp + s * 32 + i];
     const T* x = static_cast<const T*>(p.x);
     T* out = static_cast<T*>(p.out);
-    constexpr int NKW = (WM == 2) ? (((G_ + 15) / 16 * 16) + 2 * CP_) / M::KSTEP : (WM == 3 ? 2 * CP_ / M::KSTEP : 1);
-    WRegs<T, NKW> wr;
-    if constexpr (WM == 2) wr.load(static_cast<const T*>(p.wpack), s * 32 + i, dm.Cp + s * 32 + i, dm.WS, h, 0);
-    if constexpr (WM == 3) wr.load(static_cast<const T*>(p.wpack), s * 32 + i, dm.Cp + s * 32 + i, dm.WS, h, dm.KE);
     const int ch = s * 32 + i;
 
-#if MDL_FWD_ALLSLICES
     if constexpr (ST && WM == 1 && CP_ <= 64) {     // (wider static shapes: one slice per wave, the workgroup keeps that slice of W in LDS)
         // One wave handles ALL channel slices of its group.  Staging the tile (edge-feature stream, index
         // loads, x gathers, one-hot table) is slice independent: doing it once per tile instead of once per
@@ -55,15 +48,15 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
         const int nw_total = gridDim.x * (blockDim.x >> 6);
         // Two workgroups share a CU and its SIMDs arbitrate by age: the waves of the workgroup dispatched first (block index
         // below half the grid) run 14 % faster than their younger co-residents (measured wave lifetimes 161 vs 184 us), which
-        // then finish alone at half occupancy.  The older half takes MDL_FWD_AGE_SKEW per mille more of the work.
+        // then finish alone at half occupancy.  The older half takes FWD_AGE_SKEW per mille more of the work.
         NodeRange R(0, 0);
         {
             const int half = nw_total >> 1, gwu = __builtin_amdgcn_readfirstlane(gw);
-            if (MDL_FWD_AGE_SKEW == 0 || (nw_total & 1) || gridDim.x < 512) {
+            if ((nw_total & 1) || gridDim.x < 512) {
                 R = NodeRange(p, gwu, nw_total, lane);
             } else {
                 const int64_t Et = (int64_t)p.rowptr[p.N] + p.N;
-                const int64_t wa = 1000 + MDL_FWD_AGE_SKEW, wb = 1000 - MDL_FWD_AGE_SKEW;        // weights of the two halves
+                const int64_t wa = 1000 + FWD_AGE_SKEW, wb = 1000 - FWD_AGE_SKEW;        // weights of the two halves
                 auto cut = [&](int k) -> int64_t {                                               // work in front of wave k
                     const int64_t units = k <= half ? wa * k : wa * half + wb * (k - half);
                     return Et * units / (1000 * (int64_t)nw_total);
@@ -251,10 +244,10 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
 #pragma unroll
                     for (int r = 0; r < 16; ++r) { accf[r] = b0; accs[r] = b1; }
                     if constexpr (WSP != 0) {
-                        pre_tile_wsp<CP_, 1, MDL_FWD_PRE_DEPTH>(dm, w, lane, sl, 0, pf, idf, accf, accs);
+                        pre_tile_wsp<CP_, 1, FWD_PRE_DEPTH>(dm, w, lane, sl, 0, pf, idf, accf, accs);
                         pf.load(p.pt, p.ps, sl == NSL - 1 ? nxt.tgt : cur.tgt, sl == NSL - 1 ? nxt.src : cur.src, h, (sl + 1) % NSL);
                     } else {
-                        pre_tile<T, CP_, VEC, WM, NKW, MDL_FWD_PRE_DEPTH, X3>(p, dm, w, lane, sl, cur.tgt, cur.src, xf, wr, accf, accs);
+                        pre_tile<T, CP_, VEC, WM, FWD_PRE_DEPTH, X3>(p, dm, w, lane, sl, cur.tgt, cur.src, xf, accf, accs);
                     }
                     TPIN16(accf); TPIN16(accs);
                     TMARK(3 + 3 * sl);
@@ -267,11 +260,9 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
                         // the NEXT tile: more than half a tile ahead of the next wait.
                         if (sl == 0 && abq_eb >= 0) { ab_store(abq, abq_eb, abq_nv, NSL - 1); abq_eb = -1; }
                     }
-#if MDL_FWD_XEARLY
                     // the x rows of the NEXT tile: requested as soon as the last slice's MFMAs have consumed this
                     // tile's fragments (same registers), so their latency hides under the gate / aggregation
                     if constexpr (WSP == 0) { if (sl == NSL - 1) load_rows(nxt.tgt, nxt.src); }   // unconditional, like the loads above
-#endif
                     f32x16 m;
                     if constexpr (AB_) {
                         // m and, for the backward, A = dm/dpre_f = sigmoid'(f) softplus(s), B = dm/dpre_s = sigmoid(f) sigmoid(s)
@@ -305,9 +296,6 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
                     TMARK(5 + 3 * sl);
                     __builtin_amdgcn_sched_barrier(0);      // keep the slices' register footprints apart
                 }
-#if !MDL_FWD_XEARLY
-                if (!last || nextHasEdges) load_rows(nxt.tgt, nxt.src);
-#endif
                 cur = nxt;
                 TTILE();
             }
@@ -363,7 +351,6 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
         TFLUSH(0);
         return;
     }
-#endif
     // The wave walks its groups as ONE continuous stream of edge tiles: while tile t computes, the
     // indices and edge-feature words of tile t+1 are in flight — across group boundaries too — so
     // the load pipeline never drains.  A group's epilogue (residual add, mean, store) needs no
@@ -421,23 +408,17 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
         wave_lds_fence();
         TMARK(1);
 
-#ifndef MDL_ABL_NOX
         if constexpr (CP_ != 0) xf.load(x, dm.C, cur.tgt, cur.src, h);
-#endif
         // prefetch the next tile of the stream (same group, or the first tile of the next group)
         primed = false;
         if (!last) {
             nxt.template load<!ST>(p, eb + 32, G.e1, i, G.n0);
-#ifndef MDL_ABL_NOE
             if constexpr (ST) ew.prefetch(p, lane, eb + 32, min(32, G.e1 - eb - 32), nxt.ep);
-#endif
             primed = true;
         } else {
             if (hasN && GN.e0 < GN.e1) {
                 nxt.template load<!ST>(p, GN.e0, GN.e1, i, GN.n0);
-#ifndef MDL_ABL_NOE
                 if constexpr (ST) ew.prefetch(p, lane, GN.e0, min(32, GN.e1 - GN.e0), nxt.ep);
-#endif
                 primed = true;
             }
             // residual rows of this group, needed by the epilogue right after this tile
@@ -454,14 +435,7 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
         f32x16 accf, accs;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { accf[r] = bf; accs[r] = bs; }
-#ifndef MDL_ABL_NOPRE
-        pre_tile<T, CP_, VEC, WM, NKW, 0, X3>(p, dm, w, lane, s, cur.tgt, cur.src, xf, wr, accf, accs);
-#else
-        if constexpr (std::is_same<T, bf16_t>::value) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { accf[r] += bf2f((bf16_t)xf.t[0][r & 7]); accs[r] += bf2f((bf16_t)xf.s[0][r & 7]) + bf2f(w.et[i * dm.EKS + r]); }
-        }
-#endif
+        pre_tile<T, CP_, VEC, WM, 0, X3>(p, dm, w, lane, s, cur.tgt, cur.src, xf, accf, accs);
 
         TMARK(3);
         unsigned t4[4];
@@ -471,11 +445,7 @@ __global__ __launch_bounds__(MDL_FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? MD
         // contribute exact zeros to the aggregation — no per-element masking needed.
         f32x16 m;
 #pragma unroll
-#ifndef MDL_ABL_NOGATE
         for (int r = 0; r < 16; ++r) m[r] = GT::sigmoid(accf[r]) * GT::softplus_u(accs[r]);
-#else
-        for (int r = 0; r < 16; ++r) m[r] = accf[r] * accs[r];
-#endif
         TMARK(4);
         seg_reduce_cnt<T>(m, t4, i, acc_out, cnt);
         TMARK(5);

@@ -14,12 +14,9 @@
 // wave with fp32 atomics.
 #include "mdl_common.h"
 
-
-#ifndef MDL_K3C_NW
-#define MDL_K3C_NW 8        // waves per workgroup of the C = 64 node kernel (see the kernel's comment)
-#endif
-
 namespace mdl {
+
+constexpr int K3C_NW = 8;   // waves per workgroup of the C = 64 node kernel (see the kernel's comment)
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
@@ -205,9 +202,6 @@ __global__ __launch_bounds__(64 * NW, 2) void cgconv_node_stream_kernel(const bf
             // ld_out > 0 (MdlCgNode.ld_dwn): straight into the two Linears' stacked weight gradient [2C][ld_out] (rows f | s, columns
             // target | source | edge): block b of rows goes to rows (b & 1) C + c, columns (b >> 1) C + K — no assembly pass
             const int64_t at = ld_out > 0 ? (int64_t)(((R / CP) & 1) * CP + R % CP) * ld_out + ((R / CP) >> 1) * CP + K : (int64_t)R * CP + K;
-#ifdef MDL_NODE_NOFLUSH      // experiment builds only: what the atomics of the flush cost
-            if (N < 0)
-#endif
             unsafeAtomicAdd(dwn + at, dw[j][r]);
         }
     }
@@ -373,9 +367,6 @@ __global__ __launch_bounds__(64 * NW, 1) void cgconv_node_x3_kernel(const float*
         for (int r = 0; r < 16; ++r) {
             const int R = mt * 32 + d_row(r, h), K = nt * 32 + i;
             const int64_t at = ld_out > 0 ? (int64_t)(((R / CP) & 1) * CP + R % CP) * ld_out + ((R / CP) >> 1) * CP + K : (int64_t)R * CP + K;
-#ifdef MDL_NODE_NOFLUSH      // experiment builds only: what the atomics of the flush cost
-            if (N < 0)
-#endif
             unsafeAtomicAdd(dwn + at, dw[j][r]);
         }
     }
@@ -502,9 +493,9 @@ static int bwd_node_launch(const void* x, const void* grad_out, const void* r_tg
                                           // (measured 128 / 256 / 512 / 1024 blocks: 70 / 56 / 67 / 97 us)
     if (C == 64) {
         const int lds = (64 * (256 + 8) + 64 * (256 + 8) + 64 * (64 + 8)) * 2;
-        auto kf = rs16 ? cgconv_node_stream_kernel<64, true, MDL_K3C_NW> : cgconv_node_stream_kernel<64, false, MDL_K3C_NW>;
+        auto kf = rs16 ? cgconv_node_stream_kernel<64, true, K3C_NW> : cgconv_node_stream_kernel<64, false, K3C_NW>;
         set_max_dynamic_lds(reinterpret_cast<const void*>(kf), lds);
-        hipLaunchKernelGGL(kf, dim3((unsigned)sgrid), dim3(64 * MDL_K3C_NW), lds, st, (const bf16_t*)x, (const bf16_t*)grad_out,
+        hipLaunchKernelGGL(kf, dim3((unsigned)sgrid), dim3(64 * K3C_NW), lds, st, (const bf16_t*)x, (const bf16_t*)grad_out,
                            (const bf16_t*)r_tgt, r_src, (const bf16_t*)wn_t, (bf16_t*)dx, dwn, N, zero_src, ld_out);
     } else {
         const int lds = (32 * (128 + 8) + 64 * (128 + 8) + 64 * (32 + 8)) * 2;

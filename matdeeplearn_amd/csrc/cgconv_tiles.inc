@@ -12,52 +12,6 @@
 #define MDL_EXPERIMENTS 0   // 1: the experiments build (experiments/build.py): measured-negative kernel variants and their
                             // environment switches are compiled in; libmdl_hip.so itself never reads the environment
 #endif
-#ifndef MDL_CG_WM
-#define MDL_CG_WM 1       // where the static bf16 kernels keep W: 1 LDS, 2 registers, 3 x-part registers + e-part LDS
-#endif
-#ifndef MDL_FWD_XDB
-#define MDL_FWD_XDB 0     // 1: x-row gathers of tile t+1 in flight during tile t (costs 32 VGPRs)
-#endif
-#ifndef MDL_BWD_XDB
-#define MDL_BWD_XDB 1
-#endif
-#ifndef MDL_FWD_ALLSLICES
-#ifndef MDL_FWD_AGE_SKEW
-#define MDL_FWD_AGE_SKEW 60     // all-slices forward at two workgroups per CU: per mille of extra work for the older half
-#endif
-#define MDL_FWD_ALLSLICES 1   // static shapes: one forward wave handles all channel slices of its group
-#endif
-#ifndef MDL_FWD_XEARLY
-#define MDL_FWD_XEARLY 1   // all-slices forward: gather the next tile's x rows right after the last slice's MFMAs
-#endif
-#ifndef MDL_CG_PHASE_BARRIERS
-#define MDL_CG_PHASE_BARRIERS 0
-#endif
-#ifndef MDL_CG_CB_DEFAULT
-#define MDL_CG_CB_DEFAULT 0   // 1: cooperative column-block kernels for the static bf16 shapes
-#endif
-#ifndef MDL_CG_CB_BWD_DEFAULT
-#define MDL_CG_CB_BWD_DEFAULT 0   // 1: cooperative column-block backward edge pass for the static bf16 shapes
-#endif
-#ifndef MDL_CB_FWD_WG_PER_CU
-#define MDL_CB_FWD_WG_PER_CU 2
-#endif
-#ifndef MDL_FWD_PRE_DEPTH
-#define MDL_FWD_PRE_DEPTH 3   // all-slices forward: pinned LDS-read / MFMA interleave in pre_tile, reads issued ahead (-6 %)
-#endif
-#ifndef MDL_BWD_DERIV2
-#define MDL_BWD_DERIV2 0  // 1: bf16 backward with the select-free gate derivative (Gate<true>::deriv2, 3 VALU fewer per element): measured +-0
-#endif
-#ifndef MDL_FWD_RANGE_EDGES
-#define MDL_FWD_RANGE_EDGES 64   // edges per node range (= per wave) below which the launch shrinks instead: two 32-edge tiles
-#endif
-#ifndef MDL_BWD_RANGE_EDGES
-#define MDL_BWD_RANGE_EDGES 128  // (64 -> 128: -7 of 45 us at the reference's batch size — half as many waves flush their weight-gradient sums;
-                                 // from 6.5e4 edges on the grid is capped at one workgroup per CU either way)
-#endif
-#ifndef MDL_BWD_WAVES
-#define MDL_BWD_WAVES 1   // waves per SIMD the backward kernel is register-allocated for
-#endif
 
 #ifdef MDL_CG_EP_TU      // compiled a second time as cgconv_ep.hip (see the include of cgconv_ep.inc below): own debug symbols
 #define mdl_debug_life mdl_debug_life_ep
@@ -85,13 +39,8 @@ extern "C" int mdl_debug_reset() {
 #define TFLUSH(base) do { if (gw == 0 && lane == 0) { for (int _k = 0; _k < 13; ++_k) g_cg_dbg[(base) + _k] += tacc[_k]; g_cg_dbg[(base) + 15] += tcount; g_cg_dbg[(base) + 14] += clock64() - tstart; g_cg_dbg[(base) + 13] += wall_clock64() - wstart; } if (lane == 0 && gw < 4096) { g_cg_life[(base) / 16][gw][0] = wstart; g_cg_life[(base) / 16][gw][1] = wall_clock64(); g_cg_life[(base) / 16][gw][2] = tcount; } } while (0)
 #else
 #define TDECL do { } while (0)
-#if MDL_CG_PHASE_BARRIERS   // keep the phases of a tile apart in the instruction schedule (no timing)
-#define TMARK(k) __builtin_amdgcn_sched_barrier(0)
-#define TPIN16(v) do { _Pragma("unroll") for (int _r = 0; _r < 16; ++_r) asm volatile("" : "+v"(v[_r])); } while (0)
-#else
 #define TMARK(k) do { } while (0)
 #define TPIN16(v) do { } while (0)
-#endif
 #define TTILE() do { } while (0)
 #define TRESET() do { } while (0)
 #define TFLUSH(base) do { } while (0)
@@ -469,25 +418,11 @@ __device__ __forceinline__ void pre_tile_wsp(const D& dm, const WaveCtx<bf16_t>&
     }
 }
 
-// Packed weights of this wave's channel slice held in registers for the whole kernel (static
-// shapes): the B fragments of all K steps, f rows and s rows.  Removes every per-tile LDS read of W.
-template <typename T, int NK>
-struct WRegs {
-    typename Mma<T>::frag_t f[NK], s[NK];
-    __device__ __forceinline__ void load(const T* wpack, int rowf, int rows, int WS, int h, int k_first) {
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            f[k] = ld_frag(wpack, rowf, WS, k_first + k * Mma<T>::KSTEP, h);
-            s[k] = ld_frag(wpack, rows, WS, k_first + k * Mma<T>::KSTEP, h);
-        }
-    }
-};
-
 // pre-activation tile: accf/accs (32 edge slots x 32 channels of slice s), bias pre-loaded.
-template <typename T, int CP_, int VEC, int WM, int NKW, int DEPTH = 0, bool X3 = false, typename D>
+template <typename T, int CP_, int VEC, int WM, int DEPTH = 0, bool X3 = false, typename D>
 __device__ __forceinline__ void pre_tile(const CgParams& p, const D& dm, const WaveCtx<T>& w, int lane, int s,
                                          int my_tgt, int my_src, const XFrags<T, CP_, VEC, X3>& xf,
-                                         const WRegs<T, NKW>& wr, f32x16& accf, f32x16& accs) {
+                                         f32x16& accf, f32x16& accs) {
     typedef Mma<T> M;
     const int i = lane & 31, h = lane >> 5;
     const bool wsl = (CP_ == 0 || CP_ > 64) && p.w_slice;    // (never for the static shapes whose W fits LDS: folds away there)
@@ -517,42 +452,6 @@ __device__ __forceinline__ void pre_tile(const CgParams& p, const D& dm, const W
         }
         return;
     } else {
-    if constexpr (CP_ != 0 && (WM == 2 || WM == 3)) {
-        // static shapes.  WM 2: all B fragments live in registers.  WM 3: the x-part of W lives in
-        // registers, the e-part is read from the LDS copy (those reads depend on nothing and are
-        // issued at the top of the tile).
-        constexpr int NF = XFrags<T, CP_, VEC>::NF;
-        constexpr int NE = (WM == 2) ? NKW - 2 * NF : 0;
-        if constexpr (WM == 2) {
-#pragma unroll
-            for (int k = 0; k < NE; ++k) {
-                typename M::frag_t a = ld_frag(w.et, i, dm.EKS, k * M::KSTEP, h);
-                accf = M::mma(a, wr.f[k], accf);
-                accs = M::mma(a, wr.s[k], accs);
-            }
-        } else {
-#pragma unroll
-            for (int k0 = 0; k0 < dm.KE; k0 += M::KSTEP) {
-                typename M::frag_t a = ld_frag(w.et, i, dm.EKS, k0, h);
-                accf = M::mma(a, ld_frag(w.wbase, rowf, dm.WS, k0, h), accf);
-                accs = M::mma(a, ld_frag(w.wbase, rows, dm.WS, k0, h), accs);
-            }
-        }
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            accf = M::mma(xf.t[f], wr.f[NE + f], accf);
-            accs = M::mma(xf.t[f], wr.s[NE + f], accs);
-        }
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            accf = M::mma(xf.s[f], wr.f[NE + NF + f], accf);
-            accs = M::mma(xf.s[f], wr.s[NE + NF + f], accs);
-        }
-        return;
-    }
-#ifdef MDL_CG_IGLP
-    if constexpr (CP_ != 0) __builtin_amdgcn_iglp_opt(MDL_CG_IGLP);
-#endif
     // edge features (LDS tile)
 #pragma unroll
     for (int k0 = 0; k0 < dm.KE; k0 += M::KSTEP) {
@@ -562,22 +461,6 @@ __device__ __forceinline__ void pre_tile(const CgParams& p, const D& dm, const W
     }
     if constexpr (CP_ != 0) {
         constexpr int NF = XFrags<T, CP_, VEC>::NF;
-#ifdef MDL_ABL_WSPLIT_BOUND
-        // Upper bound of what the W-split (per-node projections P = x [W_tgt | W_src]^T added to the accumulators) can buy:
-        // the x part of the product as TWO MFMAs per gathered row and accumulator (what the identity-operand form of the
-        // split issues: K = 32 instead of 64) and WITHOUT their weight-fragment LDS reads; the gathers stay.  Results are
-        // wrong by construction — timing only.
-#pragma unroll
-        for (int f = 0; f < NF / 2; ++f) {
-            accf = M::mma(xf.t[f], xf.t[f + NF / 2], accf);
-            accs = M::mma(xf.t[f], xf.t[f + NF / 2], accs);
-        }
-#pragma unroll
-        for (int f = 0; f < NF / 2; ++f) {
-            accf = M::mma(xf.s[f], xf.s[f + NF / 2], accf);
-            accs = M::mma(xf.s[f], xf.s[f + NF / 2], accs);
-        }
-#else
 #pragma unroll
         for (int f = 0; f < NF; ++f) {      // target-node features (x_i)
             accf = M::mma(xf.t[f], ld_frag(w.wbase, rowf, dm.WS, dm.KE + f * M::KSTEP, h), accf);
@@ -588,16 +471,11 @@ __device__ __forceinline__ void pre_tile(const CgParams& p, const D& dm, const W
             accf = M::mma(xf.s[f], ld_frag(w.wbase, rowf, dm.WS, dm.KE + dm.Cp + f * M::KSTEP, h), accf);
             accs = M::mma(xf.s[f], ld_frag(w.wbase, rows, dm.WS, dm.KE + dm.Cp + f * M::KSTEP, h), accs);
         }
-#endif
         // Pin the schedule of the chain: DEPTH fragment reads up front, then one read behind every MFMA, so
         // that the LDS latency of a weight fragment hides under the MFMAs issued before it.  (Left alone, hipcc keeps
         // one or two reads in flight and every MFMA waits out a full LDS round trip.)
         if constexpr (DEPTH > 0 && std::is_same<T, bf16_t>::value) {
-#ifdef MDL_ABL_WSPLIT_BOUND
-            constexpr int NMMA = 2 * (D::STATIC ? ((50 + 15) / 16 + NF) : 0);
-#else
             constexpr int NMMA = 2 * (D::STATIC ? ((50 + 15) / 16 + 2 * NF) : 0);
-#endif
             __builtin_amdgcn_sched_group_barrier(0x100, DEPTH, 0);
 #pragma unroll
             for (int q = 0; q < NMMA; ++q) {

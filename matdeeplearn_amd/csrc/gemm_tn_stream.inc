@@ -270,9 +270,6 @@ __global__ __launch_bounds__(64 * NW, (MT > 4 || NT > 4) ? (NW == 8 ? 2 : 1) : 2
             }
         }
     }
-#ifdef MDL_TN_NOFLUSH      // experiment builds only: what the atomics of the flush cost (the results are then missing)
-    if (N > 0) return;
-#endif
     if (part) {
         float* const mine = part + (int64_t)blockIdx.x * (MT * NT * 1024) + lane;
 #pragma unroll

@@ -128,12 +128,8 @@ __global__ __launch_bounds__(256) void nnconv_msg_bwd_kernel(const T* __restrict
 //             dY [Co x D3]   += DM^T . H     both operands k-major over the EDGES (transpose reads), kept in registers
 // The scalar kernels above move 2 bytes per load while staging Y and keep 100 of 256 threads busy in the dot products:
 // 3.2 ms (forward) / 7.5 ms (backward) per layer on 6e4 nodes / 8e5 edges, 0.06 of the HBM roofline.
-#ifndef MDL_K7_BWD_WGS
-#define MDL_K7_BWD_WGS 2     // workgroups per CU the backward is register-allocated for (LDS allows 3)
-#endif
-#ifndef MDL_K7_BWD_SMALLC
-#define MDL_K7_BWD_SMALLC 5  // chunks per thread of the small-block form (see mdl_nnconv_msg_bwd)
-#endif
+constexpr int K7_BWD_WGS = 2;      // workgroups per CU the backward is register-allocated for (LDS allows 3)
+constexpr int K7_BWD_SMALLC = 5;   // chunks per thread of the small-block form (see mdl_nnconv_msg_bwd)
 constexpr int NM_KP = 128, NM_LD = NM_KP + 8;
 typedef __attribute__((ext_vector_type(4))) short nm_s16x4;
 typedef __attribute__((address_space(3))) nm_s16x4* nm_lds4_t;
@@ -311,7 +307,7 @@ __global__ __launch_bounds__(256, 2) void nnconv_msg_fwd_mfma_kernel(const bf16_
 }
 
 template <int MAXC>      // 16-byte chunks of Y_j per thread (5 covers 100 x 100, 7 the largest block: 128 x 112)
-__global__ __launch_bounds__(256, MAXC <= 5 ? 3 : MDL_K7_BWD_WGS) void nnconv_msg_bwd_mfma_kernel(const bf16_t* __restrict__ Y, const bf16_t* __restrict__ h,
+__global__ __launch_bounds__(256, MAXC <= 5 ? 3 : K7_BWD_WGS) void nnconv_msg_bwd_mfma_kernel(const bf16_t* __restrict__ Y, const bf16_t* __restrict__ h,
                                                                      const bf16_t* __restrict__ dm,
                                                                      const int32_t* __restrict__ rowptr_s,
                                                                      const int32_t* __restrict__ eid_s, bf16_t* __restrict__ dh,
@@ -455,11 +451,7 @@ extern "C" int mdl_nnconv_msg_fwd(const void* Y, const void* h, const int32_t* r
         // flat staging of Y_j: every node's block must start on a 16-byte boundary and fit the per-thread chunk budget
         // (D3 >= 4: the staging splits a dword index by w2 = D3 / 2 with a 32-bit reciprocal, and 2^32 / 1 does not fit one)
         const int flat = (D3 >= 4 && ((int64_t)Co * D3 * 2) % 16 == 0 && reinterpret_cast<uintptr_t>(Y) % 16 == 0 && Co * D3 <= 256 * 7 * 8) ? 1 : 0;
-#ifndef MDL_K7_YROWS_FULL
         const int yrows = flat ? Co : 128;
-#else
-        const int yrows = 128;
-#endif
         const int lds_m = (yrows + 32) * NM_LD * 2 + 32 * 4;
         (void)set_max_dynamic_lds(reinterpret_cast<const void*>(kf), (128 + 32) * NM_LD * 2 + 32 * 4);
         const unsigned w2_inv = (unsigned)((0x100000000ull + (D3 / 2) - 1) / (D3 / 2));
@@ -496,8 +488,8 @@ extern "C" int mdl_nnconv_msg_bwd(const void* Y, const void* h, const void* dm, 
         const unsigned w2_inv = (unsigned)((0x100000000ull + (D3 / 2) - 1) / (D3 / 2));
         // blocks of up to 100 x 100 (MPNN_demo) fit five chunks per thread: 8 staging registers less, which is what lets the
         // kernel be register-allocated for the three workgroups per CU its LDS allows
-        if (flat && Co * D3 <= 256 * MDL_K7_BWD_SMALLC * 8) {
-            auto kf = nnconv_msg_bwd_mfma_kernel<MDL_K7_BWD_SMALLC>;
+        if (flat && Co * D3 <= 256 * K7_BWD_SMALLC * 8) {
+            auto kf = nnconv_msg_bwd_mfma_kernel<K7_BWD_SMALLC>;
             (void)set_max_dynamic_lds(reinterpret_cast<const void*>(kf), lds_m);
             hipLaunchKernelGGL(kf, dim3((unsigned)N), dim3(256), lds_m, st, (const bf16_t*)Y, (const bf16_t*)h, (const bf16_t*)dm, rowptr_s,
                                eid_s, (bf16_t*)dh, (bf16_t*)dY, Co, D3, w2_inv, flat);

@@ -7,10 +7,6 @@
 // Algorithmic bytes: E*C*s (read) + N*C*s (write) + 4*(N+1).
 #include "mdl_common.h"
 
-#ifndef MDL_SEG_SMALL
-#define MDL_SEG_SMALL 1      // 0: the lane-group kernel for every size (A/B)
-#endif
-
 namespace mdl {
 
 __global__ __launch_bounds__(256) void csr_rowptr_kernel(const int32_t* __restrict__ idx, int64_t E, int64_t N,
@@ -244,7 +240,7 @@ static int seg_fwd(const T* src, const int32_t* rowptr, const int32_t* perm, T* 
         dim3 gv(grid_for(N * CG * 4)), bv(256);
         if (reduce != MDL_SUM && reduce != MDL_MEAN) { set_error("mdl_segment_reduce_fwd: bad reduce %d", reduce); return MDL_E_ARG; }
         // few segments (fewer lane groups than the device has lanes for): a workgroup per segment (seg_fwd_small_kernel)
-        if (MDL_SEG_SMALL && N * CG < 65536 && N <= 65535 && CG <= 256) {
+        if (N * CG < 65536 && N <= 65535 && CG <= 256) {
             dim3 gs((unsigned)N);
             if constexpr (sizeof(T) == 2) {
                 if (vw == 4) {
