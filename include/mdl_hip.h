@@ -563,6 +563,46 @@ int mdl_graph_build(const double* pos, const int64_t* node_ptr, const double* ce
                     double radius, int max_neighbors, int64_t* edge_ptr, int32_t* src, int32_t* tgt, float* dist,
                     int32_t* out_deg, int64_t edge_capacity, void* workspace, size_t workspace_bytes, mdlStream_t stream);
 
+/* ---- K1 backward: the expansion's gradient w.r.t. the distance ------------------------------
+ * No reference counterpart (the reference expands constant distances once, process.py:506-509):
+ *     dd[e] = sum_k g_out[e, k] * 2 coeff (d[e] - offsets[k]) exp(coeff (d[e] - offsets[k])^2)
+ * g_out: [E, G] row-major with leading dimension ld_g (>= G) in `g_dtype`; d / offsets / coeff as in mdl_rbf_expand;
+ * dd: [E] fp32 (written).  The exponential is recomputed from d: the forward's output is not read. */
+int mdl_rbf_expand_bwd(const void* g_out, int64_t ld_g, int g_dtype, const float* d, const float* offsets, float coeff,
+                       float* dd, int64_t E, int G, mdlStream_t stream);
+
+/* ---- K3d: CGConv gradient w.r.t. the edge features (csrc/cgconv_de.hip) ----------------------
+ * No reference counterpart as a kernel (upstream CGConv is differentiable in edge_attr through autograd; the reference
+ * model, cgcnn.py:136-145, never asks).  Inputs as mdl_cgconv_bwd_ex reads them: x [N, C], edge_attr [E, G] in CSR order,
+ * rowptr / src / tgt, wpack / bpack of mdl_cgconv_pack_weights for the plain `dtype` (not MDL_SPLIT_BF16), grad_out [N, C].
+ * Exactly one epilogue:
+ *   de != NULL  general: de [E, G] in `dtype` is written (rows of CSR slots no rowptr range covers are left alone);
+ *   dd != NULL  distance: edge_attr[e, g] = exp(coeff (d_norm[e] - offsets[g])^2); adds
+ *               scale * sum_g de[e, g] * 2 coeff (d_norm[e] - offsets[g]) edge_attr[e, g] into dd [E] fp32 (caller zero-fills
+ *               before the first layer).  No atomics: bitwise repeatable.
+ * C in 1..256, G in 1..64 (what mdl_cgconv_wpack_bytes accepts), aggr MDL_MEAN / MDL_SUM. */
+int mdl_cgconv_bwd_edge(const void* x, const void* edge_attr, const int32_t* rowptr, const int32_t* src, const int32_t* tgt,
+                        const void* wpack, const float* bpack, const void* grad_out, int64_t N, int64_t E, int C, int G,
+                        int aggr, int dtype, void* de, const float* d_norm, const float* offsets, float coeff, float scale,
+                        float* dd, mdlStream_t stream);
+
+/* ---- Edge geometry: distances of given edges as a function of the positions (csrc/edge_geom.hip) ----
+ * No reference counterpart (the reference has no force path).  Structures packed as for mdl_graph_build; src / tgt: [E] int32
+ * BATCH-GLOBAL node ids of edges src -> tgt inside one structure.
+ * fwd: dist [E] fp32 = the fp64 minimum-image |p_tgt - p_src + shift| rounded once (bitwise mdl_graph_build's value for the
+ *      pair), u [E, 3] fp32 the unit vector of that displacement (0 where dist = 0: self loops, coincident atoms).
+ *      workspace: mdl_edge_geometry_workspace_bytes(G) bytes, 8-byte aligned.
+ * bwd: dpos [N, 3] fp32 (written) = sum over in-edges dd u - sum over out-edges dd u, at fixed cell and fixed images.
+ *      rowptr_t / eid_t: CSR by target over the edges ([N + 1] slots, edge id per slot; eid NULL = the slot is the edge id);
+ *      rowptr_s / eid_s: the same by source.  No atomics: bitwise repeatable. */
+size_t mdl_edge_geometry_workspace_bytes(int64_t G);
+int mdl_edge_geometry_fwd(const double* pos, const int64_t* node_ptr, const double* cell, const int32_t* pbc, int64_t N,
+                          int64_t G, const int32_t* src, const int32_t* tgt, int64_t E, float* dist, float* u,
+                          void* workspace, size_t workspace_bytes, mdlStream_t stream);
+int mdl_edge_geometry_bwd(const float* dd, const float* u, const int32_t* rowptr_t, const int32_t* eid_t,
+                          const int32_t* rowptr_s, const int32_t* eid_s, int64_t N, int64_t E, float* dpos,
+                          mdlStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

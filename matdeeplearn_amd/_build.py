@@ -18,7 +18,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # per-file extras: the edge-per-lane CGConv backward wants its MFMA results in VGPRs (see csrc/cgconv.hip)
 # and the graph builder's fp64 distances must not be FMA-contracted (bitwise parity with the host builder, csrc/graph_build.hip)
 FILE_FLAGS = {"cgconv_ep.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "cfconv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-              "graph_build.hip": ["-ffp-contract=off"]}
+              "graph_build.hip": ["-ffp-contract=off"],
+              # the same pair distances from the shared csrc/graph_geom.inc, the same bits
+              "edge_geom.hip": ["-ffp-contract=off"]}
 # translation units that #include another .hip file
 FILE_DEPS = {}
 

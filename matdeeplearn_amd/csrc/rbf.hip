@@ -148,6 +148,30 @@ static int launch_rbf(const float* d, const float* offsets, float coeff, T* out,
     return check_launch("mdl_rbf_expand");
 }
 
+// Backward of the expansion w.r.t. the distance: dd[e] = sum_g g_out[e, g] * 2 coeff (d_e - mu_g) exp(coeff (d_e - mu_g)^2).
+// The exponential is recomputed (precise expf) from d, so the kernel never reads the forward's output and serves fp32 and bf16
+// outputs alike.  16 lanes per edge: lane j takes the features j, j + 16, ... (a wave reads four consecutive rows of g_out), the
+// partial sums meet in four xor shuffles; one lane stores the edge's value.  No atomics.
+template <typename T>
+__global__ __launch_bounds__(256) void rbf_bwd_kernel(const T* __restrict__ g_out, int64_t ld, const float* __restrict__ d,
+                                                      const float* __restrict__ offsets, float coeff, float* __restrict__ dd,
+                                                      int64_t E, int G) {
+    const int sub = threadIdx.x & 15;
+    const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    float acc = 0.0f;
+    if (e < E) {
+        const float de = d[e];
+        const T* row = g_out + e * ld;
+        for (int k = sub; k < G; k += 16) {
+            const float diff = de - offsets[k];
+            acc += Elem<T>::ld(row + k) * ((2.0f * coeff) * diff * expf(coeff * (diff * diff)));
+        }
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (e < E && sub == 0) dd[e] = acc;
+}
+
 }  // namespace mdl
 
 extern "C" int mdl_rbf_expand(const float* d, const float* offsets, float coeff, void* out, int64_t E, int G,
@@ -161,4 +185,23 @@ extern "C" int mdl_rbf_expand(const float* d, const float* offsets, float coeff,
     if (out_dtype == MDL_BF16) return launch_rbf<bf16_t>(d, offsets, coeff, (bf16_t*)out, E, G, ld_out, st);
     set_error("mdl_rbf_expand: unsupported dtype %d", out_dtype);
     return MDL_E_UNSUPP;
+}
+
+extern "C" int mdl_rbf_expand_bwd(const void* g_out, int64_t ld_g, int g_dtype, const float* d, const float* offsets, float coeff,
+                                  float* dd, int64_t E, int G, mdlStream_t stream) {
+    using namespace mdl;
+    MDL_REQUIRE(E >= 0 && G > 0 && G <= 256, MDL_E_ARG, "mdl_rbf_expand_bwd: bad E=%lld G=%d", (long long)E, G);
+    MDL_REQUIRE(ld_g >= G, MDL_E_ARG, "mdl_rbf_expand_bwd: ld_g %lld < G %d", (long long)ld_g, G);
+    if (E == 0) return MDL_OK;
+    MDL_REQUIRE(g_out && d && offsets && dd, MDL_E_ARG, "mdl_rbf_expand_bwd: null pointer");
+    MDL_REQUIRE(E < (1ll << 31) * 16, MDL_E_UNSUPP, "mdl_rbf_expand_bwd: E=%lld exceeds the grid", (long long)E);
+    const dim3 grid((unsigned)cdiv(E * 16, 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (g_dtype == MDL_F32) hipLaunchKernelGGL((rbf_bwd_kernel<float>), grid, block, 0, st, (const float*)g_out, ld_g, d, offsets, coeff, dd, E, G);
+    else if (g_dtype == MDL_BF16) hipLaunchKernelGGL((rbf_bwd_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)g_out, ld_g, d, offsets, coeff, dd, E, G);
+    else {
+        set_error("mdl_rbf_expand_bwd: unsupported dtype %d", g_dtype);
+        return MDL_E_UNSUPP;
+    }
+    return check_launch("mdl_rbf_expand_bwd");
 }

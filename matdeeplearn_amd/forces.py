@@ -1,0 +1,112 @@
+"""Forces from atomic positions: F = -dE/dpos through  positions -> minimum-image distances -> graph -> Gaussian expansion ->
+CGCNN -> prediction, all of it on the HIP device.  The reference has no force path; this is the derivative chain of the model
+the reference defines (matdeeplearn/models/cgcnn.py) on the graphs it builds (matdeeplearn/process/process.py:258-305).
+
+Chain, one public call (energy_and_forces):
+  ops.build_graphs      neighbour lists — then HELD FIXED: forces are the derivative at fixed topology, as in every k-NN graph
+                        potential (an atom that would enter or leave a neighbour list under the displacement does not)
+  ops.edge_vectors      dist(pos) of those edges, bitwise the builder's distances; backward = csrc/edge_geom.hip
+  (d - min) / (max - min)  the training set's normalisation (GraphDataset.dist_range)
+  ops.rbf_expand + models.CGCNN with ops.cgconv(dist=...): every layer's backward returns dL/dd from the fused distance epilogue
+                        of csrc/cgconv_de.hip — no [E, G] gradient is stored (fused=False: the general path through an [E, G]
+                        edge-feature gradient per layer and mdl_rbf_expand_bwd, for comparison)
+No gradient w.r.t. the cell (stress) and no second derivatives (training on forces): both raise or are absent by construction."""
+import numpy as np
+import torch
+
+from . import ops
+from .process import graph as pg
+from .process.dataset import Batch
+
+
+def _packed(structs):
+    if isinstance(structs, dict):
+        need = ("pos", "numbers", "node_ptr", "cell", "pbc")
+        if any(k not in structs for k in need):
+            raise ops.MdlError("energy_and_forces: packed arrays need the keys %s (process.graph.pack_structures)" % (need,))
+        return structs
+    return pg.pack_structures(structs)
+
+
+def _host(a, dtype):
+    return np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=dtype)
+
+
+def _node_features(numbers, out_deg, max_neighbors, dictionary, dev):
+    """x = [atom features | one-hot out-degree incl. the self loop], as process.dataset._from_structures_device builds it"""
+    z = np.asarray(numbers, dtype=np.int64)
+    uz = np.unique(z)
+    if dictionary is not None:                                 # one table row per distinct Z (graph.atom_features)
+        table = np.asarray([dictionary[str(int(v))] for v in uz], dtype=np.float32)
+    else:
+        table = pg.atom_features(uz)
+    feats = torch.from_numpy(table).to(dev).index_select(0, torch.from_numpy(np.searchsorted(uz, z)).to(dev))
+    deg = torch.zeros((len(z), max_neighbors + 2), dtype=torch.float32, device=dev)
+    deg.scatter_(1, out_deg.long().unsqueeze(1), 1.0)
+    return torch.cat([feats, deg], 1)
+
+
+def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, dictionary=None, output_index=None, fused=True):
+    """Prediction and forces F = -d(prediction)/d(positions) of a CGCNN.
+
+    model        a matdeeplearn_amd.models.CGCNN on a HIP device (other models raise MdlError: CGCNN-only for now).  Its CURRENT
+                 mode is used.  eval() is the meaningful one: in training mode BatchNorm's batch statistics couple the graphs of
+                 a batch (an atom would feel forces from other structures) and dropout makes the energy a random function.
+    structs      a list of dict(positions, numbers, cell, pbc), or the packed arrays of process.graph.pack_structures
+    dist_range   (min, max) of the TRAINING set's distance normalisation (GraphDataset.dist_range)
+    radius, max_neighbors, dictionary   as process.from_structures
+    output_index for a model with several outputs: the one to differentiate (default: the sum over the outputs)
+    fused        True: dL/dd from the fused distance epilogue of the edge-gradient kernel; False: through an [E, G] edge-feature
+                 gradient per layer (same result to rounding; for comparison)
+
+    Returns (pred [B] or [B, out] fp32, forces [N, 3] fp32, node_ptr [B + 1] int64), device tensors; atom n of structure b is row
+    node_ptr[b] + n.  The neighbour lists are built once from the given positions and HELD FIXED under the derivative; the image
+    shifts and the cell are constants too (no stress).  Forces of a graph sum to zero up to fp32 rounding; with
+    ops.deterministic() two calls return the same bits."""
+    from .models import CGCNN
+    if not isinstance(model, CGCNN):
+        raise ops.MdlError("energy_and_forces: forces are implemented for CGCNN only for now (got %s); the other models' edge paths "
+                           "lack the distance gradient (DESIGN.md)" % type(model).__name__)
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise ops.MdlError("energy_and_forces: the model must live on a HIP device (got %s)" % dev)
+    lo, hi = float(dist_range[0]), float(dist_range[1])
+    if not hi > lo:
+        raise ops.MdlError("energy_and_forces: dist_range must be (min, max) with max > min")
+    p = _packed(structs)
+    pos = torch.from_numpy(_host(p["pos"], np.float64)).to(dev)
+    node_ptr = torch.from_numpy(_host(p["node_ptr"], np.int64)).to(dev)
+    cell = torch.from_numpy(_host(p["cell"], np.float64)).to(dev)
+    pbc = torch.from_numpy(_host(p["pbc"], np.int32)).to(dev)
+    N, B = pos.shape[0], node_ptr.numel() - 1
+
+    with torch.no_grad():
+        edge_ptr, src, tgt, _, out_deg = ops.build_graphs(pos, node_ptr, cell, pbc, radius, max_neighbors)
+        E = src.numel()
+        ncnt = node_ptr[1:] - node_ptr[:-1]
+        shift = torch.repeat_interleave(node_ptr[:-1], edge_ptr[1:] - edge_ptr[:-1], output_size=E).to(torch.int32)
+        src, tgt = (src + shift).contiguous(), (tgt + shift).contiguous()          # batch-global ids, CSR by target
+        csr = ops.EdgeCSR(ops.csr_rowptr(tgt, N), src, tgt, None, N, E)
+        x = _node_features(_host(p["numbers"], np.int64), out_deg, int(max_neighbors), dictionary, dev)
+        batch_idx = torch.repeat_interleave(torch.arange(B, device=dev), ncnt, output_size=N)
+
+    with torch.enable_grad():
+        pos_g = pos.detach().requires_grad_(True)
+        dist = ops.edge_vectors(pos_g, node_ptr, cell, pbc, src, tgt, csr=csr)
+        d_norm = (dist - lo) / (hi - lo)                       # fp32, the arithmetic of GraphDataset.dist_norm
+        G, cd = model.conv_list[0].dim, model.compute_dtype
+        offsets = ops.rbf_offsets(0.0, 1.0, G, dev)
+        data = Batch(x=x, edge_weight=dist.detach(), batch=batch_idx, y=None, u=torch.zeros(B, 3, device=dev), num_graphs=B,
+                     csr=csr, num_nodes=N, num_edges=E)
+        if fused:
+            data.edge_attr = ops.rbf_expand(d_norm.detach(), 0.0, 1.0, G, 0.2, out_dtype=cd, offsets=offsets)
+            data.dist = (d_norm, offsets, ops.rbf_coeff(0.0, 1.0, 0.2))
+        else:
+            data.edge_attr = ops.rbf_expand(d_norm, 0.0, 1.0, G, 0.2, out_dtype=cd, offsets=offsets)
+        pred = model(data)
+        if pred.dim() == 2 and output_index is not None:
+            energy = pred[:, int(output_index)].sum()
+        else:
+            energy = pred.sum()
+        (gpos,) = torch.autograd.grad(energy, pos_g)
+    return pred.detach(), (-gpos).float(), node_ptr

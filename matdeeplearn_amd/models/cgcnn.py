@@ -32,10 +32,12 @@ class CGCNN(GraphModel):
         # every layer's weights are packed for the kernels in ONE launch (they are all known here): at the reference's batch size a
         # pack launch per layer is 5 us of a launch-bound step
         packs = ops.cgconv_prepack(list(self.conv_list), out.dtype, out.device, want_node=torch.is_grad_enabled()) if out.is_cuda else None
+        # force path (matdeeplearn_amd.forces): the batch says that its edge features are the expansion of data.dist[0]
+        dist = getattr(data, "dist", None)
         for i, conv in enumerate(self.conv_list):
             # conv -> bn as one call: the BatchNorm's statistics are formed in the conv kernel's epilogue where the layer has the
             # shape for it (nn.CGConv.forward); the sums' shift = the beta of the BatchNorm whose output this layer reads
             prev = self.bn_list[i - 1].bias if (bn_on and i > 0) else None
             out = self._drop(conv(out, None, edge_attr, csr=csr, bn=self.bn_list[i] if bn_on else None, bn_shift=prev,
-                                  packed=None if packs is None else packs[i], split=self.split_products))
+                                  packed=None if packs is None else packs[i], split=self.split_products, dist=dist))
         return self._head(out, data)

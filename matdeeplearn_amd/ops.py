@@ -205,15 +205,45 @@ def rbf_coeff(start=0.0, stop=1.0, width=0.2):
     return -0.5 / ((stop - start) * width) ** 2  # process.py:585
 
 
+class _RbfExpand(torch.autograd.Function):
+    """rbf_expand for distances that require a gradient: the same forward launch, mdl_rbf_expand_bwd behind it."""
+
+    @staticmethod
+    def forward(ctx, dist, offsets, coeff, out_dtype):
+        E, G = dist.numel(), offsets.numel()
+        out = torch.empty((E, G), dtype=out_dtype, device=dist.device)
+        check(lib().mdl_rbf_expand(ptr(dist), ptr(offsets), coeff, ptr(out), E, G, G, dtype_code(out), stream()), "mdl_rbf_expand")
+        ctx.save_for_backward(dist, offsets)
+        ctx.coeff = coeff
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        dist, offsets = ctx.saved_tensors
+        g = g.contiguous()
+        E, G = g.shape
+        dd = torch.empty(E, dtype=torch.float32, device=g.device)
+        check(lib().mdl_rbf_expand_bwd(ptr(g), G, dtype_code(g), ptr(dist), ptr(offsets), ctx.coeff, ptr(dd), E, G, stream()),
+              "mdl_rbf_expand_bwd")
+        return dd, None, None, None
+
+
 def rbf_expand(dist, start=0.0, stop=1.0, resolution=50, width=0.2, out_dtype=torch.float32, offsets=None,
                out=None):
-    """GaussianSmearing(start, stop, resolution, width)(dist): [E] fp32 -> [E, resolution]."""
+    """GaussianSmearing(start, stop, resolution, width)(dist): [E] fp32 -> [E, resolution].
+    Differentiable w.r.t. dist (first order: the backward recomputes the Gaussians from dist and raises on a second
+    differentiation); distances that do not require a gradient run the one launch they always did."""
     require_hip(dist)
     if dist.dtype != torch.float32:
         raise MdlError("rbf_expand: distances must be float32")
     dist = dist.contiguous()
     if offsets is None:
         offsets = rbf_offsets(start, stop, resolution, dist.device)
+    if dist.requires_grad and torch.is_grad_enabled():
+        if out is not None:
+            raise MdlError("rbf_expand: out= cannot be combined with distances that require a gradient")
+        return _RbfExpand.apply(dist, offsets.contiguous(), float(rbf_coeff(start, stop, width)), out_dtype)
     E, G = dist.numel(), offsets.numel()
     if out is None:
         out = torch.empty((E, G), dtype=out_dtype, device=dist.device)
@@ -696,11 +726,8 @@ def _take_rsrc(nfloats, device):
 
 class _CGConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, edge_attr, w_f, b_f, w_s, b_s, csr, aggr, bn=None, packed=None, split=False):
+    def forward(ctx, x, edge_attr, w_f, b_f, w_s, b_s, csr, aggr, bn=None, packed=None, split=False, d_norm=None, rbf=None):
         require_hip(x, edge_attr, w_f, w_s)
-        if edge_attr.requires_grad:
-            raise MdlError("cgconv: gradients w.r.t. edge_attr are not implemented (the reference's edge features are "
-                           "constants, cgcnn.py:136-145); detach() them or use a differentiable composition")
         if edge_attr.dtype != x.dtype:
             raise MdlError("cgconv: x (%s) and edge_attr (%s) must share a dtype" % (x.dtype, edge_attr.dtype))
         x, edge_attr = x.contiguous(), edge_attr.contiguous()
@@ -755,15 +782,32 @@ class _CGConvFn(torch.autograd.Function):
                             tgt=csr.tgt, wpack=wpack, bpack=bpack, out=out, bn_sums=bn_sums, bn_shift=bn_shift,
                             bn_rows=_true_rows_for(N) if bn_sums is not None else None)
         check(_launch_timed("fwd", lambda: L.mdl_cgconv_fwd_ex(args, stream())), "mdl_cgconv_fwd_ex")
-        ctx.save_for_backward(x, edge_attr, wf32, ws32, wpack, bpack)
+        # (d_norm, rbf): the edge features are rbf_expand(d_norm) — the backward then returns dL/dd_norm from the fused distance
+        # epilogue of the edge-gradient kernel (mdl_cgconv_bwd_edge) instead of an [E, G] gradient
+        dist_saved = () if d_norm is None else (d_norm.detach().contiguous(), rbf[0].contiguous())
+        ctx.save_for_backward(x, edge_attr, wf32, ws32, wpack, bpack, *dist_saved)
+        ctx.rbf_coeff = None if d_norm is None else float(rbf[1])
+        ctx.bias32 = (bf32, bs32)
         ctx.csr, ctx.aggr, ctx.has_bias = csr, aggr, (b_f is not None, b_s is not None)
         ctx.wdtypes = (w_f.dtype, w_s.dtype)
         ctx.C = C
         return out if Ck == C else out[:, :C].contiguous()
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        x, edge_attr, wf32, ws32, wpack, bpack = ctx.saved_tensors
+        """First order only (once_differentiable: a second differentiation raises).  The gradients of x and the weights are the
+        launches they always were; a gradient w.r.t. edge_attr (general epilogue, caller's edge order and dtype) or w.r.t. the
+        expanded distance (fused epilogue) costs one launch of the edge-gradient kernel on top."""
+        need_de = ctx.needs_input_grad[1]
+        need_dd = len(ctx.needs_input_grad) > 11 and ctx.needs_input_grad[11] and ctx.rbf_coeff is not None
+        de, dd = _cgconv_edge_grads(ctx, g, need_de, need_dd) if (need_de or need_dd) else (None, None)
+        grads = _CGConvFn._backward_main(ctx, g)
+        return grads[:1] + (de,) + grads[2:] + (dd, None)
+
+    @staticmethod
+    def _backward_main(ctx, g):
+        x, edge_attr, wf32, ws32, wpack, bpack = ctx.saved_tensors[:6]
         csr = ctx.csr
         N, Ck = x.shape                                   # Ck: the width the kernels ran at (128 for a padded layer)
         C = getattr(ctx, "C", Ck)
@@ -911,15 +955,116 @@ def cgconv_prepack(convs, x_dtype, device, want_node=True):
     return [(wbuf[k], bbuf[k], nbuf[k] if want_node else None, (C, G, dt)) for k in range(n)]
 
 
-def cgconv(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr="mean", csr=None, bn_stats=None, packed=None, split=False):
-    """CGConv forward.  x [N,C], edge_index [2,E], edge_attr [E,G]; returns [N,C].
+def cgconv(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr="mean", csr=None, bn_stats=None, packed=None, split=False, dist=None):
+    """CGConv forward.  x [N,C], edge_index [2,E], edge_attr [E,G]; returns [N,C].  Differentiable (first order) in
+    x, the weights and edge_attr, like upstream's operator; the edge_attr gradient comes back in the caller's edge order and in
+    edge_attr's dtype from one extra launch (csrc/cgconv_de.hip), and only when edge_attr requires it.
     bn_stats = (sums [2 R + 3, C] fp32 zero-filled, shift [C] fp32 or None): the kernel's epilogue also forms the statistics
-    of its output for the BatchNorm behind the layer (callers check cgconv_bn_stats_ok first)."""
+    of its output for the BatchNorm behind the layer (callers check cgconv_bn_stats_ok first).
+    dist = (d_norm [E] fp32, offsets [G] fp32, coeff): a promise that edge_attr = rbf_expand(d_norm) on these centres (detached:
+    edge_attr itself carries no gradient).  The backward then hands d_norm its gradient from the kernel's fused distance epilogue,
+    and no [E, G] gradient is ever stored.  Under split=True ("bf16x3") the edge-gradient kernel runs its exact fp32 form."""
     if aggr not in ("mean", "add", "sum"):
         raise MdlError("cgconv: aggr must be mean or add")
     if csr is None:
         csr = csr_for(edge_index, x.shape[0])
-    return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], bn_stats, packed, split)
+    if dist is None:
+        return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], bn_stats, packed, split)
+    d_norm, offsets, coeff = dist
+    require_hip(d_norm, offsets)
+    if d_norm.dtype != torch.float32 or d_norm.numel() != edge_attr.shape[0] or offsets.numel() != edge_attr.shape[1]:
+        raise MdlError("cgconv: dist = (d_norm [E] float32, offsets [G], coeff) must match edge_attr %s" % (tuple(edge_attr.shape),))
+    return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], bn_stats, packed, split, d_norm,
+                           (offsets.float(), float(coeff)))
+
+
+def _bwd_edge_launch(x, ea_sorted, csr, wpack, bpack, g, aggr, C, G, de=None, d_sorted=None, offsets=None, coeff=0.0, scale=1.0, dd=None):
+    """mdl_cgconv_bwd_edge on CSR-ordered operands: de [E, G] (general epilogue) or dd [E] += (distance epilogue)."""
+    check(_launch_timed("bwd_edge", lambda: lib().mdl_cgconv_bwd_edge(
+        ptr(x), ptr(ea_sorted), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(bpack), ptr(g), x.shape[0], ea_sorted.shape[0],
+        C, G, aggr, dtype_code(x), ptr(de), ptr(d_sorted), ptr(offsets), float(coeff), float(scale), ptr(dd), stream())),
+        "mdl_cgconv_bwd_edge")
+
+
+def _plain_pack(wf32, bf32, ws32, bs32, C, G, dt, device):
+    wpack = torch.empty(lib().mdl_cgconv_wpack_bytes(C, G, dt), dtype=torch.uint8, device=device)
+    bpack = torch.empty(2 * _rup(C, 32), dtype=torch.float32, device=device)
+    check(lib().mdl_cgconv_pack_weights(ptr(wf32), ptr(bf32), ptr(ws32), ptr(bs32), C, G, ptr(wpack), ptr(bpack), dt, stream()),
+          "mdl_cgconv_pack_weights")
+    return wpack, bpack
+
+
+def _unsort_edges(t, csr):
+    """a per-edge tensor in CSR order -> the caller's edge order"""
+    if csr.eperm is None:
+        return t
+    out = torch.empty_like(t)
+    out[csr.eperm.long()] = t
+    return out
+
+
+def _cgconv_edge_grads(ctx, g, need_de, need_dd):
+    """The per-edge gradients of one CGConv layer (see _CGConvFn.backward): (de or None, dd or None) in the caller's edge order."""
+    saved = ctx.saved_tensors
+    x, edge_attr, wf32, ws32, wpack, bpack = saved[:6]
+    csr = ctx.csr
+    C = ctx.C
+    E, G = edge_attr.shape
+    dt = dtype_code(x)
+    if x.shape[1] != C:
+        x = x[:, :C].contiguous()                         # a padded layer: the edge-gradient kernel runs at the true width
+    g = g.contiguous()
+    if getattr(ctx, "split", 0):                          # bf16x3 layer: exact fp32 form on plainly packed weights
+        wpack, bpack = _plain_pack(wf32, ctx.bias32[0], ws32, ctx.bias32[1], C, G, dt, x.device)
+    de = dd = None
+    if need_de:
+        de = (torch.zeros if csr.partial else torch.empty)((E, G), dtype=edge_attr.dtype, device=x.device)
+        _bwd_edge_launch(x, edge_attr, csr, wpack, bpack, g, ctx.aggr, C, G, de=de)
+        de = _unsort_edges(de, csr)
+    if need_dd:
+        d_norm, offsets = saved[6], saved[7]
+        d_sorted = d_norm if csr.eperm is None else d_norm.index_select(0, csr.eperm.long())
+        dd = torch.zeros(E, dtype=torch.float32, device=x.device)
+        _bwd_edge_launch(x, edge_attr, csr, wpack, bpack, g, ctx.aggr, C, G, d_sorted=d_sorted, offsets=offsets, coeff=ctx.rbf_coeff, dd=dd)
+        dd = _unsort_edges(dd, csr)
+    return de, dd
+
+
+def cgconv_dist_grad(x, edge_index, d_norm, w_f, b_f, w_s, b_s, grad_out, aggr="mean", csr=None, start=0.0, stop=1.0, resolution=50,
+                     width=0.2, scale=1.0, edge_attr=None, out=None):
+    """dL/dd of ONE CGConv layer whose edge features are the Gaussian expansion rbf_expand(d_norm, start, stop, resolution, width)
+    in x's dtype, for the output gradient grad_out [N, C]: the fused distance epilogue of the edge-gradient kernel
+    (csrc/cgconv_de.hip) —  scale * sum_g de[e, g] * d e[e, g] / d d_norm[e]  per edge, with de kept in registers.
+    `scale` is the chain-rule factor of the caller's normalisation (1 / (max - min) for raw distances).  Returns [E] fp32 in the
+    caller's edge order; `out` ([E] fp32, CSR-ordered edge lists only) is added into instead, so that the layers of a model
+    accumulate in one buffer.  No atomics: bitwise repeatable.  No gradient flows through this call itself."""
+    if aggr not in ("mean", "add", "sum"):
+        raise MdlError("cgconv_dist_grad: aggr must be mean or add")
+    require_hip(x, d_norm, w_f, w_s, grad_out)
+    if csr is None:
+        csr = csr_for(edge_index, x.shape[0])
+    with torch.no_grad():
+        N, C = x.shape
+        G, E = int(resolution), d_norm.numel()
+        if d_norm.dtype != torch.float32 or E != csr.E or csr.N != N:
+            raise MdlError("cgconv_dist_grad: d_norm must be [E] float32 over the CSR's %d edges" % csr.E)
+        if out is not None and csr.eperm is not None:
+            raise MdlError("cgconv_dist_grad: out= needs an edge list in CSR (target-sorted) order")
+        dt = dtype_code(x)
+        if lib().mdl_cgconv_wpack_bytes(C, G, dt) == 0:
+            raise MdlError("cgconv_dist_grad: unsupported C=%d G=%d" % (C, G))
+        offsets = rbf_offsets(start, stop, G, x.device)
+        d_sorted = (d_norm if csr.eperm is None else d_norm.index_select(0, csr.eperm.long())).contiguous()
+        if edge_attr is None:
+            ea = rbf_expand(d_sorted.detach(), start, stop, G, width, out_dtype=x.dtype, offsets=offsets)
+        else:
+            ea = csr.sorted_attr(edge_attr.detach().contiguous())
+        f32 = lambda t: None if t is None else t.detach().float().contiguous()
+        wpack, bpack = _plain_pack(f32(w_f), f32(b_f), f32(w_s), f32(b_s), C, G, dt, x.device)
+        dd = out if out is not None else torch.zeros(E, dtype=torch.float32, device=x.device)
+        _bwd_edge_launch(x.detach().contiguous(), ea, csr, wpack, bpack, grad_out.detach().to(x.dtype).contiguous(), _lib.REDUCE[aggr], C, G,
+                         d_sorted=d_sorted, offsets=offsets, coeff=rbf_coeff(start, stop, width), scale=scale, dd=dd)
+        return dd if out is not None else _unsort_edges(dd, csr)
 
 
 # BatchNorm statistics in the CGConv forward's epilogue (mdl_cgconv_fwd_ex, bn_sums): OPT-IN.  Measured on the bench batch
@@ -2103,3 +2248,60 @@ def build_graphs(pos, node_ptr, cell, pbc, radius=8.0, max_neighbors=12):
     edge_ptr, src, tgt, dist, out_deg = _build_graphs_launch(pos, node_ptr, cell, pbc, G, radius, max_neighbors)
     E = int(edge_ptr[-1])
     return edge_ptr, src[:E], tgt[:E], dist[:E], out_deg
+
+
+# ------------------------------------------------------------------------------------------------
+# Edge geometry: distances of given edges as a differentiable function of the positions (csrc/edge_geom.hip)
+# ------------------------------------------------------------------------------------------------
+class _EdgeVectors(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, node_ptr, cell, pbc, src, tgt, csr):
+        N, G, E = pos.shape[0], node_ptr.numel() - 1, src.numel()
+        dist = torch.empty(E, dtype=torch.float32, device=pos.device)
+        u = torch.empty((E, 3), dtype=torch.float32, device=pos.device)
+        nbytes = lib().mdl_edge_geometry_workspace_bytes(G)
+        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=pos.device)
+        check(lib().mdl_edge_geometry_fwd(ptr(pos), ptr(node_ptr), ptr(cell), ptr(pbc), N, G, ptr(src), ptr(tgt), E, ptr(dist), ptr(u),
+                                          ptr(ws), nbytes, stream()), "mdl_edge_geometry_fwd")
+        ctx.save_for_backward(u, src, tgt)
+        ctx.csr, ctx.N, ctx.pos_dtype = csr, N, pos.dtype
+        ctx.mark_non_differentiable(u)
+        return dist, u
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_dist, _g_u):
+        u, src, tgt = ctx.saved_tensors
+        csr = ctx.csr
+        if csr is None:                                    # one sort by target and one by source, both stable: deterministic
+            csr = build_csr(torch.stack([src, tgt]), ctx.N)
+        rowptr_s, _, eid_s, _ = csr.transposed()
+        dpos = torch.empty((ctx.N, 3), dtype=torch.float32, device=u.device)
+        check(lib().mdl_edge_geometry_bwd(ptr(g_dist.float().contiguous()), ptr(u), ptr(csr.rowptr), ptr(csr.eperm), ptr(rowptr_s), ptr(eid_s),
+                                          ctx.N, u.shape[0], ptr(dpos), stream()), "mdl_edge_geometry_bwd")
+        return dpos.to(ctx.pos_dtype), None, None, None, None, None, None
+
+
+def edge_vectors(pos, node_ptr, cell, pbc, src, tgt, edge_ptr=None, csr=None, return_unit=False):
+    """Minimum-image distances of GIVEN edges, differentiable (first order) w.r.t. the positions.
+      pos / node_ptr / cell / pbc as in build_graphs; src / tgt [E] int32: edges src -> tgt inside a structure.  With edge_ptr
+      ([G + 1] int64, as build_graphs returns it) the ids are graph-local, otherwise batch-global.
+    Returns dist [E] fp32 — for the edges build_graphs returned, bitwise the dist it returned (the same device code chooses the
+    image: reduced cell, completed basis, rint wrap, +-1 images) — and with return_unit=True also u [E, 3] fp32, the unit vector
+    of the displacement p_tgt - p_src + shift (0 for self loops and coincident atoms; carries no gradient).
+    The backward is dpos[tgt] += g u, dpos[src] -= g u as two segmented sums (by target and by source: no atomics, bitwise
+    repeatable).  The image shifts and the cell are held fixed: there is no gradient w.r.t. `cell` (stress is out of scope).
+    csr: an EdgeCSR of the batch-global edge list, if the caller has one (saves the backward its two sorts)."""
+    pos, node_ptr, cell, pbc, G = _graph_args(pos, node_ptr, cell, pbc)
+    require_hip(src, tgt)
+    if src.dtype != torch.int32 or tgt.dtype != torch.int32 or src.shape != tgt.shape or src.dim() != 1:
+        raise MdlError("edge_vectors: src / tgt must be [E] int32")
+    if pos.shape[0] < 1:
+        raise MdlError("edge_vectors: no atoms")
+    if edge_ptr is not None:
+        shift = torch.repeat_interleave(node_ptr[:-1], edge_ptr[1:] - edge_ptr[:-1], output_size=src.numel()).to(torch.int32)
+        src, tgt = src + shift, tgt + shift
+    if csr is not None and (csr.N != pos.shape[0] or csr.E != src.numel()):
+        raise MdlError("edge_vectors: csr does not match the edge list")
+    dist, u = _EdgeVectors.apply(pos, node_ptr, cell, pbc, src.contiguous(), tgt.contiguous(), csr)
+    return (dist, u) if return_unit else dist
