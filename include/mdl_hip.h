@@ -530,6 +530,28 @@ int mdl_cfconv_bwd_w(const void* rbf, const float* cut, const void* h, const voi
 /* out[e, :] = a[ia[e], :] * b[ib[e], :] * scale[e]   (gradient w.r.t. the per-edge filter w) */
 int mdl_edge_mul(const void* a, const int32_t* ia, const void* b, const int32_t* ib, const float* scale, void* out,
                  int64_t E, int64_t F, int dtype, mdlStream_t stream);
+/* out[e] = sum_c a[ia[e], c] * b[ib[e], c] * w[e, c]  (w NULL: ones), fp32 — the gradient of mdl_gather_mul_reduce w.r.t. its
+ * per-edge scale (a = grad_out, ia = target per edge, b = h, ib = source per edge, all in the caller's edge order): the cosine
+ * cutoff of CFConv, the normalisation of GCNConv.  fp32 and bf16 inputs; one wave per edge, no atomics (bitwise repeatable). */
+int mdl_edge_dot(const void* a, const int32_t* ia, const void* b, const int32_t* ib, const void* w, float* out, int64_t E,
+                 int64_t F, int dtype, mdlStream_t stream);
+/* K4d (csrc/cfconv_de.hip) — the CFConv gradients w.r.t. the PER-EDGE inputs, with a_e and the filter W_e recomputed (no
+ * reference counterpart: schnet.py:131-145 feeds constant edge features).  Operands as mdl_cfconv_bwd_w reads them (CSR order;
+ * rows past rowptr[N] are ignored and their outputs left alone).  bf16: wpack of mdl_cfconv_pack_weights (w1 .. b2 unused), the
+ * shapes of mdl_cfconv_supported, a_e / W_e / c q / da rounded to bf16 where the forward and K4b round them.  fp32: the masters
+ * w1 [F, G], b1 [F] or NULL, w2 [F, F], b2 [F] or NULL (wpack unused), exact fp32 products, F in [33, 160], G in [1, 64] while
+ * the weights fit the LDS (mdl_cfconv_bwd_edge_supported; F = 150, G = 50 does).  Other shapes: MDL_E_UNSUPP.  Outputs:
+ *   dcut != NULL  dcut[e] = sum_f g[tgt_e, f] h[src_e, f] W_e[f], fp32 (the gradient w.r.t. the cutoff factor);
+ *   drbf != NULL  general epilogue: drbf [E, G] in `dtype`, the gradient w.r.t. the edge features;
+ *   dd != NULL    distance epilogue: rbf[e, k] = exp(coeff (d_norm[e] - offsets[k])^2); adds
+ *                 scale * sum_k drbf[e, k] * 2 coeff (d_norm[e] - offsets[k]) rbf[e, k] into dd [E] fp32 (the caller zero-fills
+ *                 before the first block); drbf stays in registers.
+ * At most one of drbf / dd.  No atomics: bitwise repeatable. */
+int mdl_cfconv_bwd_edge_supported(int F, int G, int dtype);
+int mdl_cfconv_bwd_edge(const void* rbf, const float* cut, const void* h, const void* g, const int32_t* rowptr, const int32_t* src,
+                        const int32_t* tgt, const void* wpack, const float* w1, const float* b1, const float* w2, const float* b2,
+                        int64_t N, int64_t E, int F, int G, int dtype, float* dcut, void* drbf, const float* d_norm,
+                        const float* offsets, float coeff, float scale, float* dd, mdlStream_t stream);
 
 /* ---- split-product ("bf16x3") parity mode: operand preparation for the TN GEMM -------------------------
  * hi[k] + lo[k] = src[k] to 16 significant bits (bf16 pair, both rounded to nearest even), so that a fp32 product runs on the

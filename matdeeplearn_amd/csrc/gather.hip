@@ -67,6 +67,30 @@ __global__ __launch_bounds__(256) void edge_mul_kernel(const T* __restrict__ a, 
     }
 }
 
+// dscale[e] = sum_c a[ia[e], c] * b[ib[e], c] * w[e, c]   (w == nullptr: ones) — the gradient of mdl_gather_mul_reduce w.r.t. its
+// per-edge scale (a = grad_out gathered by target, b = h gathered by source).  One wave per edge: the lanes stride the row, the
+// wave's sum is a fixed shuffle tree (no atomics: the same bits on every run)
+template <typename T>
+__global__ __launch_bounds__(256) void edge_dot_kernel(const T* __restrict__ a, const int32_t* __restrict__ ia,
+                                                       const T* __restrict__ b, const int32_t* __restrict__ ib,
+                                                       const T* __restrict__ w, float* __restrict__ out, int64_t E, int F) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * 4;
+    for (int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); e < E; e += stride) {
+        const T* ar = a + (int64_t)ia[e] * F;
+        const T* br = b + (int64_t)ib[e] * F;
+        float acc = 0.0f;
+        for (int c = lane; c < F; c += 64) {
+            float v = Elem<T>::ld(ar + c) * Elem<T>::ld(br + c);
+            if (w) v *= Elem<T>::ld(w + e * F + c);
+            acc += v;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (lane == 0) out[e] = acc;
+    }
+}
+
 // ---- two-channel (dword) versions for bf16 rows with an even channel count (SchNet: F = 150 -> 75 dwords per row) ----
 // One thread owns one dword of one output row; the threads of a row are consecutive, so every gathered h row and every w
 // row is read as one contiguous run; rows are walked four slots at a time with all loads issued before the first use.
@@ -241,6 +265,21 @@ extern "C" int mdl_edge_mul(const void* a, const int32_t* ia, const void* b, con
         hipLaunchKernelGGL((edge_mul_kernel<bf16_t>), dim3(g_grid(E * F)), dim3(256), 0, st, (const bf16_t*)a, ia, (const bf16_t*)b, ib, scale, (bf16_t*)out, E, (int)F);
     else { set_error("mdl_edge_mul: unsupported dtype %d", dtype); return MDL_E_UNSUPP; }
     return check_launch("mdl_edge_mul");
+}
+
+extern "C" int mdl_edge_dot(const void* a, const int32_t* ia, const void* b, const int32_t* ib, const void* w, float* out,
+                            int64_t E, int64_t F, int dtype, mdlStream_t stream) {
+    using namespace mdl;
+    MDL_REQUIRE(E >= 0 && F > 0 && F < (1ll << 31) && (E == 0 || (a && ia && b && ib && out)), MDL_E_ARG, "mdl_edge_dot: bad arguments");
+    if (E == 0) return MDL_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv(E, 4), 256 * 32);
+    if (dtype == MDL_F32)
+        hipLaunchKernelGGL((edge_dot_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)a, ia, (const float*)b, ib, (const float*)w, out, E, (int)F);
+    else if (dtype == MDL_BF16)
+        hipLaunchKernelGGL((edge_dot_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)a, ia, (const bf16_t*)b, ib, (const bf16_t*)w, out, E, (int)F);
+    else { set_error("mdl_edge_dot: unsupported dtype %d", dtype); return MDL_E_UNSUPP; }
+    return check_launch("mdl_edge_dot");
 }
 
 extern "C" int mdl_ssp_bwd(const void* g, const void* y, void* dx, int64_t n, int dtype, mdlStream_t stream) {

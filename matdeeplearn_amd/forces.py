@@ -1,5 +1,5 @@
 """Forces from atomic positions: F = -dE/dpos through  positions -> minimum-image distances -> graph -> Gaussian expansion ->
-CGCNN -> prediction, all of it on the HIP device.  The reference has no force path; this is the derivative chain of the model
+CGCNN or SchNet -> prediction, all of it on the HIP device.  The reference has no force path; this is the derivative chain of the model
 the reference defines (matdeeplearn/models/cgcnn.py) on the graphs it builds (matdeeplearn/process/process.py:258-305).
 
 Chain, one public call (energy_and_forces):
@@ -10,6 +10,8 @@ Chain, one public call (energy_and_forces):
   ops.rbf_expand + models.CGCNN with ops.cgconv(dist=...): every layer's backward returns dL/dd from the fused distance epilogue
                         of csrc/cgconv_de.hip — no [E, G] gradient is stored (fused=False: the general path through an [E, G]
                         edge-feature gradient per layer and mdl_rbf_expand_bwd, for comparison)
+  models.SchNet with ops.cfconv(dist=...): the same through csrc/cfconv_de.hip, plus the second route — the cosine cutoff of the
+                        RAW distance scales every message, so edge_weight carries a gradient and every block returns dL/dcut
 No gradient w.r.t. the cell (stress) and no second derivatives (training on forces): both raise or are absent by construction."""
 import numpy as np
 import torch
@@ -46,10 +48,11 @@ def _node_features(numbers, out_deg, max_neighbors, dictionary, dev):
     return torch.cat([feats, deg], 1)
 
 
-def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, dictionary=None, output_index=None, fused=True):
-    """Prediction and forces F = -d(prediction)/d(positions) of a CGCNN.
+def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, dictionary=None, output_index=None, fused=True,
+                      routes=("expansion", "cutoff")):
+    """Prediction and forces F = -d(prediction)/d(positions) of a CGCNN or a SchNet.
 
-    model        a matdeeplearn_amd.models.CGCNN on a HIP device (other models raise MdlError: CGCNN-only for now).  Its CURRENT
+    model        a matdeeplearn_amd.models.CGCNN or .SchNet on a HIP device (GCN / MPNN / MEGNet raise MdlError).  Its CURRENT
                  mode is used.  eval() is the meaningful one: in training mode BatchNorm's batch statistics couple the graphs of
                  a batch (an atom would feel forces from other structures) and dropout makes the energy a random function.
     structs      a list of dict(positions, numbers, cell, pbc), or the packed arrays of process.graph.pack_structures
@@ -59,17 +62,22 @@ def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, 
     fused        True: dL/dd from the fused distance epilogue of the edge-gradient kernel; False: through an [E, G] edge-feature
                  gradient per layer (same result to rounding; for comparison)
 
+    routes       diagnostic (SchNet): which of the two ways the distance enters carries the derivative — "expansion" (the Gaussian
+                 expansion that feeds the filter network) and / or "cutoff" (the cosine cutoff of the raw distance).  The default,
+                 both, is the force; one alone is that route's share (the two shares add up to the force).
+
     Returns (pred [B] or [B, out] fp32, forces [N, 3] fp32, node_ptr [B + 1] int64), device tensors; atom n of structure b is row
     node_ptr[b] + n.  The neighbour lists are built once from the given positions and HELD FIXED under the derivative; the image
     shifts and the cell are constants too (no stress).  Forces of a graph sum to zero up to fp32 rounding; with
     ops.deterministic() two calls return the same bits."""
-    from .models import CGCNN
-    if not isinstance(model, CGCNN):
-        raise ops.MdlError("energy_and_forces: forces are implemented for CGCNN only for now (got %s); the other models' edge paths "
+    from .models import CGCNN, SchNet
+    if not isinstance(model, (CGCNN, SchNet)):
+        raise ops.MdlError("energy_and_forces: forces are implemented for CGCNN and SchNet (got %s); the other models' edge paths "
                            "lack the distance gradient (DESIGN.md)" % type(model).__name__)
+    schnet = isinstance(model, SchNet)
     dev = next(model.parameters()).device
     if dev.type != "cuda":
-        raise ops.MdlError("energy_and_forces: the model must live on a HIP device (got %s)" % dev)
+        raise ops.MdlError("energy_and_forces: the model must be a CGCNN or SchNet on a HIP device (got %s)" % dev)
     lo, hi = float(dist_range[0]), float(dist_range[1])
     if not hi > lo:
         raise ops.MdlError("energy_and_forces: dist_range must be (min, max) with max > min")
@@ -94,9 +102,13 @@ def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, 
         pos_g = pos.detach().requires_grad_(True)
         dist = ops.edge_vectors(pos_g, node_ptr, cell, pbc, src, tgt, csr=csr)
         d_norm = (dist - lo) / (hi - lo)                       # fp32, the arithmetic of GraphDataset.dist_norm
-        G, cd = model.conv_list[0].dim, model.compute_dtype
+        if "expansion" not in routes:
+            d_norm = d_norm.detach()
+        G = model.conv_list[0].mlp[0].in_features if schnet else model.conv_list[0].dim
+        cd = model.compute_dtype
         offsets = ops.rbf_offsets(0.0, 1.0, G, dev)
-        data = Batch(x=x, edge_weight=dist.detach(), batch=batch_idx, y=None, u=torch.zeros(B, 3, device=dev), num_graphs=B,
+        # SchNet's energy depends on the distance through the expansion AND through the cosine cutoff of the raw distance
+        data = Batch(x=x, edge_weight=dist if schnet and "cutoff" in routes else dist.detach(), batch=batch_idx, y=None, u=torch.zeros(B, 3, device=dev), num_graphs=B,
                      csr=csr, num_nodes=N, num_edges=E)
         if fused:
             data.edge_attr = ops.rbf_expand(d_norm.detach(), 0.0, 1.0, G, 0.2, out_dtype=cd, offsets=offsets)

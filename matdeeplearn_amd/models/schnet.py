@@ -25,6 +25,8 @@ class SchNet(GraphModel):
         out = self._pre(x)
         cut = cosine_cutoff(data.edge_weight, self.conv_list[0].conv.cutoff) if len(self.conv_list) else None   # once per batch
         by_source = ops.BySourceAttrs()                 # the backward's by-source copy of (edge_attr, cut): made once, by the last block
+        dist = getattr(data, "dist", None)              # forces: edge_attr = rbf_expand(d_norm), see ops.cfconv
         for i, conv in enumerate(self.conv_list):
-            out = self._drop(self._bn(i, out + conv(out, None, data.edge_weight, edge_attr, csr=csr, cut=cut, by_source=by_source)))
+            out = self._drop(self._bn(i, out + conv(out, None, data.edge_weight, edge_attr, csr=csr, cut=cut, by_source=by_source,
+                                                    dist=dist)))
         return self._head(out, data)

@@ -182,17 +182,30 @@ class CFConv(nn.Module):
         nn.init.xavier_uniform_(self.lin2.weight)
         self.lin2.bias.data.fill_(0)
 
-    def forward(self, x, edge_index, edge_weight, edge_attr, csr=None, cut=None, by_source=None):
-        return _lin(self.lin2, self.aggregate(x, edge_index, edge_weight, edge_attr, csr=csr, cut=cut, by_source=by_source))
+    def forward(self, x, edge_index, edge_weight, edge_attr, csr=None, cut=None, by_source=None, dist=None):
+        return _lin(self.lin2, self.aggregate(x, edge_index, edge_weight, edge_attr, csr=csr, cut=cut, by_source=by_source, dist=dist))
 
-    def aggregate(self, x, edge_index, edge_weight, edge_attr, csr=None, cut=None, by_source=None):
+    def aggregate(self, x, edge_index, edge_weight, edge_attr, csr=None, cut=None, by_source=None, dist=None):
         """sum_j lin1(x)_j * W(e_ij) * C(d_ij): the convolution in front of lin2 (InteractionBlock chains lin2 -> ssp -> lin as
-        ONE fused sequence behind it)"""
+        ONE fused sequence behind it).
+        dist = (d_norm [E] fp32, offsets [G], coeff): edge_attr = rbf_expand(d_norm), detached (ops.cfconv).  A gradient asked
+        of the edge inputs (dist, edge_attr, the cutoff) is served by ops.cfconv (csrc/cfconv_de.hip) where the shape allows,
+        otherwise by the general composition below (the dense layers' input gradient + the scale gradient of
+        ops.gather_mul_reduce); with none asked the routing is what it always was."""
         if csr is None:
             csr = ops.csr_for(edge_index, x.shape[0])
         c = cosine_cutoff(edge_weight, self.cutoff) if cut is None else cut           # [E] fp32
         h = _lin(self.lin1, x)
         mods = list(self.nn)
+        if torch.is_grad_enabled() and (c.requires_grad or edge_attr.requires_grad or (dist is not None and dist[0].requires_grad)):
+            if (len(mods) == 3 and isinstance(mods[0], nn.Linear) and isinstance(mods[1], ShiftedSoftplus) and isinstance(mods[2], nn.Linear)
+                    and edge_attr.dtype == h.dtype and ops.cfconv_edge_ok(edge_attr, h, mods[0].weight, mods[2].weight)):
+                return ops.cfconv(edge_attr, c, h, csr, mods[0], mods[2], dist=dist)
+            if dist is not None and dist[0].requires_grad:
+                # a shape K4d does not take: the expansion itself carries the gradient ([E, G] per block)
+                edge_attr = ops._RbfExpand.apply(dist[0].contiguous(), dist[1].float().contiguous(), float(dist[2]), edge_attr.dtype)
+            w = _seq(self.nn, edge_attr)
+            return ops.gather_mul_reduce(h, csr, w=w.to(h.dtype), scale=c, reduce="sum")
         if (len(mods) == 3 and isinstance(mods[0], nn.Linear) and isinstance(mods[1], ShiftedSoftplus) and isinstance(mods[2], nn.Linear)
                 and ops.cfconv_fused_ok(edge_attr, h, csr, mods[0], mods[2])):
             if (ops._CFCONV_RECOMPUTE and h.shape[1] >= ops._CFCONV_RECOMPUTE_MIN_F and not c.requires_grad
@@ -231,10 +244,10 @@ class InteractionBlock(nn.Module):
         nn.init.xavier_uniform_(self.lin.weight)
         self.lin.bias.data.fill_(0)
 
-    def forward(self, x, edge_index, edge_weight, edge_attr, csr=None, cut=None, by_source=None):
+    def forward(self, x, edge_index, edge_weight, edge_attr, csr=None, cut=None, by_source=None, dist=None):
         # lin(ssp(lin2(agg))) as one chain: fused dense layers with the activation in the first one's epilogue and its derivative
         # handed down from the second one's backward (no softplus / softplus_backward passes over [N, C])
-        agg = self.conv.aggregate(x, edge_index, edge_weight, edge_attr, csr=csr, cut=cut, by_source=by_source)
+        agg = self.conv.aggregate(x, edge_index, edge_weight, edge_attr, csr=csr, cut=cut, by_source=by_source, dist=dist)
         return _seq([self.conv.lin2, self.act, self.lin], agg)
 
 

@@ -1132,9 +1132,6 @@ class _GatherMulReduce(torch.autograd.Function):
     def forward(ctx, h, w, scale, csr, reduce, pre=None):
         # pre: the result, already formed by the fused CFConv forward (cfconv_fused) — this node then only records the graph
         require_hip(h)
-        if scale is not None and scale.requires_grad:
-            raise MdlError("gather_mul_reduce: gradients w.r.t. the per-edge scale are not implemented (cutoff / GCN "
-                           "norm are functions of constant distances on the reference path)")
         h = h.contiguous()
         N, F = csr.N, h.shape[1]
         if w is not None:
@@ -1163,6 +1160,14 @@ class _GatherMulReduce(torch.autograd.Function):
             deg = (csr.rowptr[1:] - csr.rowptr[:-1]).clamp(min=1).to(g.dtype)
             g = g / deg.unsqueeze(1)
         dh = dw = None
+        if scale is not None and ctx.needs_input_grad[2]:
+            # dscale[e] = sum_f g[tgt_e, f] h[src_e, f] w[e, f] (mdl_edge_dot): the cosine cutoff of CFConv as a function of the
+            # positions; GCNConv's normalised gather-reduce gets the same gradient for free
+            dscale = torch.empty(csr.E, dtype=torch.float32, device=h.device)
+            check(lib().mdl_edge_dot(ptr(g), ptr(csr.col), ptr(h), ptr(csr.row), ptr(w), ptr(dscale), csr.E, h.shape[1],
+                                     dtype_code(h), stream()), "mdl_edge_dot")
+            dh, dw = _gmr_dh_dw(ctx, g, h, w, scale, csr)
+            return dh, dw, dscale, None, None, None
         if (w is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _GMR_DW and h.dtype == torch.bfloat16
                 and h.shape[1] % 2 == 0 and h.shape[1] <= 512 and scale is not None):
             # one walk over the by-source CSR gives both gradients (no mdl_edge_mul pass)
@@ -1173,21 +1178,30 @@ class _GatherMulReduce(torch.autograd.Function):
             check(lib().mdl_gather_mul_reduce_dw(ptr(g), ptr(w), ptr(scale), ptr(rowptr_s), ptr(col_s), ptr(eid_s), ptr(dh), ptr(h),
                                                  ptr(dw), csr.N, h.shape[1], dtype_code(h), stream()), "mdl_gather_mul_reduce_dw")
             return dh, dw, None, None, None, None
-        if ctx.needs_input_grad[0]:
-            rowptr_s, col_s, eid_s, _ = csr.transposed()
-            dh = torch.empty_like(h)
-            check(lib().mdl_gather_mul_reduce(ptr(g), ptr(w), ptr(scale), ptr(rowptr_s), ptr(col_s), ptr(eid_s),
-                                              ptr(dh), csr.N, h.shape[1], _lib.MDL_SUM, dtype_code(h), stream()),
-                  "mdl_gather_mul_reduce(T)")
-        if w is not None and ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            check(lib().mdl_edge_mul(ptr(h), ptr(csr.row), ptr(g), ptr(csr.col), ptr(scale), ptr(dw), csr.E,
-                                     h.shape[1], dtype_code(h), stream()), "mdl_edge_mul")
+        dh, dw = _gmr_dh_dw(ctx, g, h, w, scale, csr)
         return dh, dw, None, None, None, None
 
 
+def _gmr_dh_dw(ctx, g, h, w, scale, csr):
+    """(dh, dw) of _GatherMulReduce by the two separate launches: the transposed gather-reduce and mdl_edge_mul"""
+    dh = dw = None
+    if ctx.needs_input_grad[0]:
+        rowptr_s, col_s, eid_s, _ = csr.transposed()
+        dh = torch.empty_like(h)
+        check(lib().mdl_gather_mul_reduce(ptr(g), ptr(w), ptr(scale), ptr(rowptr_s), ptr(col_s), ptr(eid_s),
+                                          ptr(dh), csr.N, h.shape[1], _lib.MDL_SUM, dtype_code(h), stream()),
+              "mdl_gather_mul_reduce(T)")
+    if w is not None and ctx.needs_input_grad[1]:
+        dw = torch.empty_like(w)
+        check(lib().mdl_edge_mul(ptr(h), ptr(csr.row), ptr(g), ptr(csr.col), ptr(scale), ptr(dw), csr.E,
+                                 h.shape[1], dtype_code(h), stream()), "mdl_edge_mul")
+    return dh, dw
+
+
 def gather_mul_reduce(h, csr, w=None, scale=None, reduce="sum", pre=None):
-    """out[i] = reduce_{edges k -> i} h[src_k] * w[k] * scale[k]  (w: [E,F], scale: [E], caller's edge order)."""
+    """out[i] = reduce_{edges k -> i} h[src_k] * w[k] * scale[k]  (w: [E,F], scale: [E], caller's edge order).
+    Differentiable in h, w and scale (scale: [E] fp32 from mdl_edge_dot, only when it requires a gradient — SchNet's cutoff as a
+    function of the positions; GCNConv's edge normalisation gets the same gradient for free)."""
     return _GatherMulReduce.apply(h, w, scale, csr, _lib.REDUCE[reduce], pre)
 
 
@@ -1313,6 +1327,211 @@ class _CFConvRecompute(torch.autograd.Function):
 def cfconv_recompute(rbf, cut, h, csr, lin_a, lin_b, cache=None):
     """K4 + K4b: the CFConv aggregation as ONE autograd node that stores nothing per edge (see cfconv_fused_ok for the shapes)."""
     return _CFConvRecompute.apply(rbf, cut, h, lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias, csr, cache)
+
+
+# ------------------------------------------------------------------------------------------------
+# K4d — CFConv gradients w.r.t. the per-edge inputs (csrc/cfconv_de.hip): forces for SchNet
+# ------------------------------------------------------------------------------------------------
+# launches of mdl_cfconv_bwd_edge by epilogue (tests assert that the kernel, not the general composition, served a case)
+K4D_LAUNCHES = collections.Counter()
+
+
+def cfconv_edge_ok(rbf, h, w1, w2):
+    """mdl_cfconv_bwd_edge takes these operands: bf16 at the shapes of the fused forward, fp32 while the weights fit the LDS"""
+    if not (rbf.is_cuda and rbf.dim() == 2 and h.dim() == 2 and rbf.dtype == h.dtype and h.dtype in (torch.float32, torch.bfloat16)):
+        return False
+    F, G = h.shape[1], rbf.shape[1]
+    if tuple(w1.shape) != (F, G) or tuple(w2.shape) != (F, F):
+        return False
+    return bool(lib().mdl_cfconv_bwd_edge_supported(F, G, dtype_code(h)))
+
+
+def _cfconv_bwd_edge_launch(rbf_s, cut_s, h, g, csr, wpack, w1, b1, w2, b2, dcut=None, drbf=None, d_sorted=None, offsets=None,
+                            coeff=0.0, scale=1.0, dd=None):
+    """mdl_cfconv_bwd_edge on CSR-ordered operands"""
+    K4D_LAUNCHES["distance" if dd is not None else ("general" if drbf is not None else "dcut")] += 1
+    F, G = h.shape[1], rbf_s.shape[1]
+    check(_launch_timed("cfconv_bwd_edge", lambda: lib().mdl_cfconv_bwd_edge(
+        ptr(rbf_s), ptr(cut_s), ptr(h), ptr(g), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(w1), ptr(b1), ptr(w2),
+        ptr(b2), csr.N, csr.E, F, G, dtype_code(h), ptr(dcut), ptr(drbf), ptr(d_sorted), ptr(offsets), float(coeff), float(scale),
+        ptr(dd), stream())), "mdl_cfconv_bwd_edge")
+
+
+def _sort_edges(t, csr):
+    return t if csr.eperm is None else t.index_select(0, csr.eperm.long())
+
+
+def _filter_f32(rbf, w1, b1, w2, b2):
+    a = torch.nn.functional.softplus(torch.nn.functional.linear(rbf, w1, b1)) - 0.6931471805599453
+    return torch.nn.functional.linear(a, w2, b2)
+
+
+class _CFConvEdge(torch.autograd.Function):
+    """The CFConv aggregation as ONE autograd node that is also differentiable in its per-edge inputs (first order).
+    forward: bf16 = mdl_cfconv_fwd without activations; fp32 = the filter network + mdl_gather_mul_reduce.  backward: dh as
+    the training path forms it, the parameter gradients only for parameters that need them, and K4d for the edge inputs: dcut
+    for the cutoff, the distance epilogue for d_norm (dist given), the general epilogue for rbf."""
+
+    @staticmethod
+    def forward(ctx, rbf, cut, h, w1, b1, w2, b2, csr, d_norm, meta):
+        require_hip(rbf, h, cut)
+        F, G = h.shape[1], rbf.shape[1]
+        dev = h.device
+        bf = h.dtype == torch.bfloat16
+        h = h.contiguous()
+        rbf_s = csr.sorted_attr(rbf.contiguous())
+        cut_s = _sort_edges(cut.float(), csr).contiguous()
+        f32 = lambda t: None if t is None else t.detach().float().contiguous()
+        w1f, b1f, w2f, b2f = f32(w1), f32(b1), f32(w2), f32(b2)
+        out = torch.empty((csr.N, F), dtype=h.dtype, device=dev)
+        wpack = None
+        if bf:
+            wpack = torch.empty(lib().mdl_cfconv_wpack_bytes(), dtype=torch.uint8, device=dev)
+            check(lib().mdl_cfconv_pack_weights(ptr(w1f), ptr(b1f), ptr(w2f), ptr(b2f), F, G, ptr(wpack), stream()), "mdl_cfconv_pack_weights")
+            check(_launch_timed("cfconv_fwd", lambda: lib().mdl_cfconv_fwd(
+                ptr(rbf_s), ptr(cut_s), ptr(h), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(out), None, None, csr.N,
+                csr.E, F, G, dtype_code(h), stream())), "mdl_cfconv_fwd")
+        else:
+            w_s = _filter_f32(rbf_s, w1f, b1f, w2f, b2f).contiguous()
+            check(lib().mdl_gather_mul_reduce(ptr(h), ptr(w_s), ptr(cut_s), ptr(csr.rowptr), ptr(csr.src), None, ptr(out), csr.N, F,
+                                              _lib.MDL_SUM, dtype_code(h), stream()), "mdl_gather_mul_reduce")
+        ctx.csr, ctx.meta, ctx.has_b = csr, meta, (b1 is not None, b2 is not None)
+        ctx.save_for_backward(rbf_s, cut_s, h, wpack, w1f, b1f, w2f, b2f, d_norm)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        rbf_s, cut_s, h, wpack, w1f, b1f, w2f, b2f, d_norm = ctx.saved_tensors
+        csr = ctx.csr
+        N, E, F, G = csr.N, csr.E, h.shape[1], rbf_s.shape[1]
+        bf = h.dtype == torch.bfloat16
+        g = g.contiguous()
+        need = ctx.needs_input_grad
+        drbf = dcut = dh = dw1 = db1 = dw2 = db2 = ddn = None
+        if need[2]:
+            rowptr_s, col_s, eid_s, src_sorted = csr.transposed()
+            # (eid_s numbers the caller's edges; the saved rows are in CSR order: compose with the inverse of eperm)
+            if csr.eperm is None:
+                pos_s = eid_s
+            else:
+                inv = torch.empty_like(csr.eperm)
+                inv[csr.eperm.long()] = torch.arange(E, dtype=csr.eperm.dtype, device=h.device)
+                pos_s = inv.index_select(0, eid_s.long())
+            dh = torch.empty_like(h)
+            if bf:
+                rbf_t, cut_t = BySourceAttrs().get(rbf_s, cut_s, pos_s.contiguous())
+                check(_launch_timed("cfconv_bwd_h", lambda: lib().mdl_cfconv_fwd(
+                    ptr(rbf_t), ptr(cut_t), ptr(g), ptr(rowptr_s), ptr(col_s), ptr(src_sorted), ptr(wpack), ptr(dh), None, None, N, E, F,
+                    G, dtype_code(h), stream())), "mdl_cfconv_fwd(T)")
+            else:
+                w_s = _filter_f32(rbf_s, w1f, b1f, w2f, b2f).contiguous()
+                check(lib().mdl_gather_mul_reduce(ptr(g), ptr(w_s), ptr(cut_s), ptr(rowptr_s), ptr(col_s), ptr(pos_s.contiguous()), ptr(dh),
+                                                  N, F, _lib.MDL_SUM, dtype_code(h), stream()), "mdl_gather_mul_reduce(T)")
+        if need[3] or need[4] or need[5] or need[6]:
+            if bf:
+                buf = torch.zeros(F * G + F * F + 2 * F, dtype=torch.float32, device=h.device)
+                dw1, dw2 = buf[:F * G].view(F, G), buf[F * G:F * G + F * F].view(F, F)
+                db1 = buf[F * G + F * F:F * G + F * F + F] if ctx.has_b[0] else None
+                db2 = buf[F * G + F * F + F:] if ctx.has_b[1] else None
+                scratch = torch.empty(lib().mdl_cfconv_bwd_w_scratch_bytes(), dtype=torch.uint8, device=h.device)
+                check(_launch_timed("cfconv_bwd_w", lambda: lib().mdl_cfconv_bwd_w(
+                    ptr(rbf_s), ptr(cut_s), ptr(h), ptr(g), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(dw1), ptr(db1),
+                    ptr(dw2), ptr(db2), ptr(scratch), N, E, F, G, dtype_code(h) | _dflag(), stream())), "mdl_cfconv_bwd_w")
+            else:
+                # fp32: the filter gradient by mdl_edge_mul, the two dense layers' parameter gradients by the library
+                dwf = torch.empty((E, F), dtype=h.dtype, device=h.device)
+                check(lib().mdl_edge_mul(ptr(h), ptr(csr.src), ptr(g), ptr(csr.tgt), ptr(cut_s), ptr(dwf), E, F, dtype_code(h), stream()),
+                      "mdl_edge_mul")
+                if csr.partial:
+                    dwf[int(csr.rowptr[-1]):] = 0
+                pre = torch.nn.functional.linear(rbf_s, w1f, b1f)
+                a = torch.nn.functional.softplus(pre) - 0.6931471805599453
+                dw2, db2 = dwf.t() @ a, (dwf.sum(0) if ctx.has_b[1] else None)
+                da = (dwf @ w2f) * torch.sigmoid(pre)
+                dw1, db1 = da.t() @ rbf_s, (da.sum(0) if ctx.has_b[0] else None)
+        want_dd = d_norm is not None and need[8]
+        if need[0] or need[1] or want_dd:
+            if need[1]:
+                dcut = (torch.zeros if csr.partial else torch.empty)(E, dtype=torch.float32, device=h.device)
+            if need[0]:
+                drbf = (torch.zeros if csr.partial else torch.empty)((E, G), dtype=rbf_s.dtype, device=h.device)
+                _cfconv_bwd_edge_launch(rbf_s, cut_s, h, g, csr, wpack, w1f, b1f, w2f, b2f, dcut=None if want_dd else dcut, drbf=drbf)
+                drbf = _unsort_edges(drbf, csr)
+            if want_dd:
+                offsets, coeff = ctx.meta
+                ddn = torch.zeros(E, dtype=torch.float32, device=h.device)
+                _cfconv_bwd_edge_launch(rbf_s, cut_s, h, g, csr, wpack, w1f, b1f, w2f, b2f, dcut=dcut, d_sorted=_sort_edges(d_norm, csr).contiguous(),
+                                        offsets=offsets, coeff=coeff, dd=ddn)
+                ddn = _unsort_edges(ddn, csr)
+            elif need[1] and not need[0]:
+                _cfconv_bwd_edge_launch(rbf_s, cut_s, h, g, csr, wpack, w1f, b1f, w2f, b2f, dcut=dcut)
+            if dcut is not None:
+                dcut = _unsort_edges(dcut, csr)
+        return drbf, dcut, dh, dw1, db1, dw2, db2, None, ddn, None
+
+
+def cfconv(rbf, cut, h, csr, lin_a, lin_b, dist=None):
+    """CFConv aggregation  out_i = sum_{e: j -> i} h_j * W(rbf_e) * cut_e  (W = lin_b(ssp(lin_a(.)))) as one autograd node
+    differentiable in rbf [E, G], cut [E] and h (and the filter network's parameters): what a force evaluation needs.  The
+    per-edge gradients come from ONE extra launch of csrc/cfconv_de.hip, in the caller's edge order and dtype, only for inputs
+    that require them.  Callers check cfconv_edge_ok first (other shapes: the general composition of nn.CFConv.aggregate).
+    dist = (d_norm [E] fp32, offsets [G] fp32, coeff): a promise that rbf = rbf_expand(d_norm) on these centres (detached).  The
+    backward then hands d_norm its gradient from the kernel's fused distance epilogue; no [E, G] gradient is ever stored."""
+    if not cfconv_edge_ok(rbf, h, lin_a.weight, lin_b.weight):
+        raise MdlError("cfconv: unsupported shape F=%d G=%d %s (mdl_cfconv_bwd_edge_supported)" % (h.shape[1], rbf.shape[1], h.dtype))
+    if rbf.shape[0] != csr.E:
+        raise MdlError("cfconv: rbf must have one row per edge of the CSR")
+    if dist is None:
+        return _CFConvEdge.apply(rbf, cut, h, lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias, csr, None, None)
+    d_norm, offsets, coeff = dist
+    require_hip(d_norm, offsets)
+    if d_norm.dtype != torch.float32 or d_norm.numel() != rbf.shape[0] or offsets.numel() != rbf.shape[1]:
+        raise MdlError("cfconv: dist = (d_norm [E] float32, offsets [G], coeff) must match rbf %s" % (tuple(rbf.shape),))
+    return _CFConvEdge.apply(rbf.detach(), cut, h, lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias, csr, d_norm,
+                             (offsets.float().contiguous(), float(coeff)))
+
+
+def cfconv_dist_grad(h, edge_index, d_norm, cut, w1, b1, w2, b2, grad_out, csr=None, start=0.0, stop=1.0, resolution=50, width=0.2,
+                     scale=1.0, edge_attr=None, out=None, want_dcut=False):
+    """dL/dd of ONE CFConv aggregation whose edge features are rbf_expand(d_norm, start, stop, resolution, width) in h's dtype,
+    for the output gradient grad_out [N, F]: the fused distance epilogue of csrc/cfconv_de.hip (the [E, G] gradient stays in
+    registers).  cut [E]: the cutoff factors (constants here).  `scale` is the chain-rule factor of the caller's normalisation.
+    Returns [E] fp32 in the caller's edge order — or (dd, dcut) with want_dcut, dcut [E] fp32 the gradient w.r.t. the cutoff
+    factor; `out` ([E] fp32, CSR-ordered edge lists only) is added into instead, so that the blocks of a model accumulate in one
+    buffer.  No atomics: bitwise repeatable.  No gradient flows through this call itself."""
+    require_hip(h, d_norm, w1, w2, grad_out, cut)
+    if csr is None:
+        csr = csr_for(edge_index, h.shape[0])
+    with torch.no_grad():
+        N, F = h.shape
+        G, E = int(resolution), d_norm.numel()
+        if d_norm.dtype != torch.float32 or E != csr.E or csr.N != N:
+            raise MdlError("cfconv_dist_grad: d_norm must be [E] float32 over the CSR's %d edges" % csr.E)
+        if out is not None and csr.eperm is not None:
+            raise MdlError("cfconv_dist_grad: out= needs an edge list in CSR (target-sorted) order")
+        dt = dtype_code(h)
+        if not lib().mdl_cfconv_bwd_edge_supported(F, G, dt):
+            raise MdlError("cfconv_dist_grad: unsupported F=%d G=%d" % (F, G))
+        offsets = rbf_offsets(start, stop, G, h.device)
+        d_sorted = _sort_edges(d_norm, csr).contiguous()
+        if edge_attr is None:
+            ea = rbf_expand(d_sorted.detach(), start, stop, G, width, out_dtype=h.dtype, offsets=offsets)
+        else:
+            ea = csr.sorted_attr(edge_attr.detach().contiguous())
+        f32 = lambda t: None if t is None else t.detach().float().contiguous()
+        w1f, b1f, w2f, b2f = f32(w1), f32(b1), f32(w2), f32(b2)
+        wpack = None
+        if h.dtype == torch.bfloat16:
+            wpack = torch.empty(lib().mdl_cfconv_wpack_bytes(), dtype=torch.uint8, device=h.device)
+            check(lib().mdl_cfconv_pack_weights(ptr(w1f), ptr(b1f), ptr(w2f), ptr(b2f), F, G, ptr(wpack), stream()), "mdl_cfconv_pack_weights")
+        dd = out if out is not None else torch.zeros(E, dtype=torch.float32, device=h.device)
+        dcut = torch.zeros(E, dtype=torch.float32, device=h.device) if want_dcut else None
+        _cfconv_bwd_edge_launch(ea, _sort_edges(cut.detach().float(), csr).contiguous(), h.detach().contiguous(),
+                                grad_out.detach().to(h.dtype).contiguous(), csr, wpack, w1f, b1f, w2f, b2f, dcut=dcut, d_sorted=d_sorted,
+                                offsets=offsets, coeff=rbf_coeff(start, stop, width), scale=scale, dd=dd)
+        dd = dd if out is not None else _unsort_edges(dd, csr)
+        return (dd, _unsort_edges(dcut, csr)) if want_dcut else dd
 
 
 # ------------------------------------------------------------------------------------------------
