@@ -16,6 +16,19 @@ import torch
 from . import _lib
 from ._lib import MdlError, check, dtype_code, lib, ptr, require_hip, stream
 
+_ACT_CODE = {"relu": 1, "ssp": 2}        # activation codes of the dense kernels (0 = none)
+_LN2 = 0.6931471805599453                # the shift of the shifted softplus
+
+
+def _f32c(t):
+    """t as a detached, contiguous fp32 tensor (None stays None): how the packing kernels read weights and biases"""
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _stream_key(device):
+    """key of the per-device, per-stream buffer tables"""
+    return (device.index, torch.cuda.current_stream(device).cuda_stream)
+
 
 # ------------------------------------------------------------------------------------------------
 # CSR-by-target graph index
@@ -91,22 +104,14 @@ class EdgeCSR:
     def row(self):
         """source of every edge in the CALLER's edge order (int32)"""
         if self._row is None:
-            if self.eperm is None:
-                self._row = self.src
-            else:
-                self._row = torch.empty_like(self.src)
-                self._row[self.eperm.long()] = self.src
+            self._row = _unsort_edges(self.src, self)
         return self._row
 
     @property
     def col(self):
         """target of every edge in the caller's edge order (int32)"""
         if self._col is None:
-            if self.eperm is None:
-                self._col = self.tgt
-            else:
-                self._col = torch.empty_like(self.tgt)
-                self._col[self.eperm.long()] = self.tgt
+            self._col = _unsort_edges(self.tgt, self)
         return self._col
 
     def transposed(self):
@@ -555,7 +560,7 @@ _WS = {}
 def _workspace(device, nbytes):
     """Per-device scratch for the kernels' work counters (the library zeroes what it uses on the stream; launches on one
     stream are ordered, so the layers of a model share it)."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    key = _stream_key(device)
     t = _WS.get(key)
     if t is None or t.numel() < nbytes:
         t = _WS[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
@@ -579,7 +584,7 @@ def _tn_scratch(device, rows=None):
     than the handful of atomics it replaces."""
     if not _TN_SCRATCH or (rows is not None and rows < _TN_SCRATCH_MIN_ROWS):
         return None
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    key = _stream_key(device)
     t = _TNS.get(key)
     if t is None:
         t = _TNS[key] = torch.empty(lib().mdl_tn_scratch_bytes(), dtype=torch.uint8, device=device)
@@ -717,7 +722,7 @@ def _take_rsrc(nfloats, device):
         ent = _RSRC.pop(max(cand, key=lambda k: _RSRC[k][0].numel()))
         owned.append(ent)
         return ent
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    key = _stream_key(device)
     ent = _RSRC.get(key)
     if ent is None or ent[0].numel() < nfloats or ent[1]:
         ent = _RSRC[key] = [torch.zeros(int(nfloats), dtype=torch.float32, device=device), False]
@@ -743,9 +748,7 @@ class _CGConvFn(torch.autograd.Function):
         sp = _lib.MDL_SPLIT_BF16 if (split and dt == _lib.MDL_F32 and G == 50 and E > 0 and not _DET
                                      and ((C == 64 and x.data_ptr() % 16 == 0) or (_PAD128 and 96 < C <= 128))) else 0
         ctx.split = sp
-        wf32, ws32 = w_f.detach().float().contiguous(), w_s.detach().float().contiguous()
-        bf32 = None if b_f is None else b_f.detach().float().contiguous()
-        bs32 = None if b_s is None else b_s.detach().float().contiguous()
+        wf32, ws32, bf32, bs32 = _f32c(w_f), _f32c(w_s), _f32c(b_f), _f32c(b_s)
         nbytes = L.mdl_cgconv_wpack_bytes(C, G, dt | sp)
         if nbytes == 0:
             raise MdlError("cgconv: unsupported C=%d G=%d" % (C, G))
@@ -756,22 +759,19 @@ class _CGConvFn(torch.autograd.Function):
         if _PAD128 and (dt == _lib.MDL_BF16 or sp) and G == 50 and 96 < C < 128 and (csr.eperm is None or sp) and E > 0:
             Ck = 128
             x = torch.nn.functional.pad(x, (0, Ck - C))
+        use_packed = packed is not None and packed[3] == (C, G, dt)
         wn_t = None
-        if packed is not None and packed[3] == (C, G, dt):
+        if use_packed:
             wpack, bpack, wn_t = packed[:3]               # packed with the model's other layers (cgconv_prepack): no launch here
-        else:
+        elif dt == _lib.MDL_BF16 and (C in (32, 64) or Ck == 128) and any(ctx.needs_input_grad):
+            # a training step on the K3c shapes packs the backward node kernel's operand in the same launch
             wpack = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
             bpack = torch.empty(2 * _rup(C, 32), dtype=torch.float32, device=x.device)
-        # a training step on the K3c shapes packs the backward node kernel's operand in the same launch
-        if packed is not None and packed[3] == (C, G, dt):
-            pass
-        elif dt == _lib.MDL_BF16 and (C in (32, 64) or Ck == 128) and any(ctx.needs_input_grad):
             wn_t = torch.empty((C, 4 * _rup(C, 32)), dtype=torch.bfloat16, device=x.device)
             check(L.mdl_cgconv_pack_weights_node(ptr(wf32), ptr(bf32), ptr(ws32), ptr(bs32), C, G, ptr(wpack), ptr(bpack),
                                                  ptr(wn_t), dt, stream()), "mdl_cgconv_pack_weights_node")
         else:
-            check(L.mdl_cgconv_pack_weights(ptr(wf32), ptr(bf32), ptr(ws32), ptr(bs32), C, G, ptr(wpack), ptr(bpack), dt | sp,
-                                            stream()), "mdl_cgconv_pack_weights")
+            wpack, bpack = _plain_pack(wf32, bf32, ws32, bs32, C, G, dt | sp, x.device, nbytes)
         ctx.wn_t = wn_t
         out = torch.empty_like(x)
         edge_attr = csr.sorted_attr(edge_attr)          # CSR order: the kernels never go through eperm
@@ -810,7 +810,7 @@ class _CGConvFn(torch.autograd.Function):
         x, edge_attr, wf32, ws32, wpack, bpack = ctx.saved_tensors[:6]
         csr = ctx.csr
         N, Ck = x.shape                                   # Ck: the width the kernels ran at (128 for a padded layer)
-        C = getattr(ctx, "C", Ck)
+        C = ctx.C
         E, G = edge_attr.shape
         Cp, GP = _rup(C, 32), _rup(G, 64)
         g = g.contiguous()
@@ -820,7 +820,7 @@ class _CGConvFn(torch.autograd.Function):
             gk = torch.nn.functional.pad(g, (0, Ck - C))
             x = x[:, :C]                                  # (the node-level part below works on the true width)
         r_tgt = torch.empty((N, 2 * Cp), dtype=x.dtype, device=x.device)          # by-target sums, compute dtype
-        sp = getattr(ctx, "split", 0)
+        sp = ctx.split
         node_x3 = bool(sp) and dt == _lib.MDL_F32 and C == 64                  # split-product node kernel (fp32 storage)
         node_hip = (dt == _lib.MDL_BF16 and C == Cp and C in (32, 64)) or node_x3   # K3c consumes r_tgt / r_src
         rs16 = (_RSRC16 and dt == _lib.MDL_BF16 and (node_hip or Ck == 128) and G == 50 and E > 0
@@ -852,18 +852,14 @@ class _CGConvFn(torch.autograd.Function):
         fl = _dflag()
         # node ranges of equal COST (far sources make a tile dearer): one prefix per batch, shared by all layers
         bal = csr.balance() if (rs16 and _BALANCE and E >= 400000 and not fl) else None
-        eargs = _lib.cg_args(dtype=dt, flags=fl | (_k3flag() if rs16 else 0) | getattr(ctx, "split", 0), aggr=ctx.aggr, N=N, E=E, C=Ck, G=G, x=xk, edge_attr=edge_attr,
+        eargs = _lib.cg_args(dtype=dt, flags=fl | (_k3flag() if rs16 else 0) | sp, aggr=ctx.aggr, N=N, E=E, C=Ck, G=G, x=xk, edge_attr=edge_attr,
                              rowptr=csr.rowptr, src=csr.src, tgt=csr.tgt, wpack=wpack, bpack=bpack, grad_out=gk, r_tgt=r_tgt, r_src=r_src,
                              r_src_dtype=_lib.MDL_BF16 if rs16 else _lib.MDL_F32, dwe=dwe, ld_dwe=ld_dwe, db=db, workspace=ws,
                              workspace_bytes=ws.numel(), balance=bal)
         check(_launch_timed("bwd", lambda: lib().mdl_cgconv_bwd_ex(eargs, stream())), "mdl_cgconv_bwd_ex")
         # node-level dense part: rows of Wn / dWn = (f_tgt, s_tgt, f_src, s_src)
         if node_hip:
-            wn_t, ctx.wn_t = getattr(ctx, "wn_t", None), None                                      # Wn^T (packed by the forward)
-            if wn_t is None:
-                wn_t = torch.empty((C, 4 * Cp), dtype=torch.float32 if node_x3 else torch.bfloat16, device=x.device)
-                check(lib().mdl_cgconv_pack_node_weights(ptr(wf32), ptr(ws32), C, G, ptr(wn_t), dt, stream()),
-                      "mdl_cgconv_pack_node_weights")
+            wn_t = _node_weights(ctx, C, Cp, torch.float32 if node_x3 else torch.bfloat16, x.device, wf32, ws32)
             dx = torch.empty_like(x)
             nargs = _lib.cg_node_args(dtype=dt, flags=fl | (sp if node_x3 else 0), zero_src=1 if keep is not None else 0, N=N, C=C,
                                       r_src_dtype=_lib.MDL_BF16 if rs16 else _lib.MDL_F32, ld_dwn=ldw if direct else 0, x=x, grad_out=g,
@@ -872,16 +868,12 @@ class _CGConvFn(torch.autograd.Function):
             if keep is not None:
                 keep[1] = False                                                                     # handed back zeroed
             if direct:
-                return (dx, None, dW[:C].to(ctx.wdtypes[0]), db[:C].to(ctx.wdtypes[0]) if ctx.has_bias[0] else None,
-                        dW[C:].to(ctx.wdtypes[1]), db[C:].to(ctx.wdtypes[1]) if ctx.has_bias[1] else None, None, None, None, None, None)
-            dW_f = torch.empty((C, 2 * C + G), dtype=torch.float32, device=x.device)
-            dW_s = torch.empty_like(dW_f)
-            db_f = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_bias[0] else None
-            db_s = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_bias[1] else None
-            check(_launch_timed("bwd_grads", lambda: lib().mdl_cgconv_assemble_grads(
-                ptr(dwn), ptr(dwe), ptr(db), C, G, ptr(dW_f), ptr(dW_s), ptr(db_f), ptr(db_s), stream())), "mdl_cgconv_assemble_grads")
-            return dx, None, dW_f.to(ctx.wdtypes[0]), db_f, dW_s.to(ctx.wdtypes[1]), db_s, None, None, None, None, None
-        if dt == _lib.MDL_BF16 and Cp == 128 and C % 2 == 0 and N > 0:
+                dW_f, dW_s = dW[:C], dW[C:]
+                db_f = db[:C].to(ctx.wdtypes[0]) if ctx.has_bias[0] else None
+                db_s = db[C:].to(ctx.wdtypes[1]) if ctx.has_bias[1] else None
+            else:
+                dW_f, db_f, dW_s, db_s = _assemble_grads(ctx, dwn, dwe, db, C, G, x.device, timed=True)
+        elif dt == _lib.MDL_BF16 and Cp == 128 and C % 2 == 0 and N > 0:
             # wide layers (C = 100 / 128): the same products on the streaming kernels.  r_tgt / r_src keep their padded
             # [N, 2 Cp] layout (padded columns are exact zeros), so  dx = g + r_tgt Wn_t + r_src Wn_s  is two library GEMMs on
             # zero-padded weights (no gather / cat of the four column blocks) and  dWn = [r_tgt | r_src]^T x  four TN-GEMM
@@ -891,37 +883,49 @@ class _CGConvFn(torch.autograd.Function):
             # Wn^T [C, 4 Cp] (columns f_tgt | s_tgt | f_src | s_src, zero-padded to Cp each) comes packed with the forward's weights
             # (one launch for all layers: cgconv_prepack) — round 6; before, the two zero-padded operands were built here with
             # eight fill / slice-copy / cast launches per layer
-            wn_t, ctx.wn_t = getattr(ctx, "wn_t", None), None
-            if wn_t is None:
-                wn_t = torch.empty((C, 4 * Cp), dtype=torch.bfloat16, device=x.device)
-                check(lib().mdl_cgconv_pack_node_weights(ptr(wf32), ptr(ws32), C, G, ptr(wn_t), dt, stream()),
-                      "mdl_cgconv_pack_node_weights")
+            wn_t = _node_weights(ctx, C, Cp, torch.bfloat16, x.device, wf32, ws32)
             dx = torch.addmm(g, r_tgt, wn_t[:, :2 * Cp].t())
             dx.addmm_(rs_b, wn_t[:, 2 * Cp:].t())
             xc = x.contiguous()
             for blk, r in enumerate((r_tgt[:, :Cp], r_tgt[:, Cp:], rs_b[:, :Cp], rs_b[:, Cp:])):
                 check(_gemm_tn(r, r.stride(0), Cp, None, 0, 0, xc, xc.stride(0), C, dwn[blk * Cp:(blk + 1) * Cp], None, N, dt | fl,
                                x.device), "mdl_gemm_tn")
-            dW_f = torch.empty((C, 2 * C + G), dtype=torch.float32, device=x.device)
-            dW_s = torch.empty_like(dW_f)
-            db_f = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_bias[0] else None
-            db_s = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_bias[1] else None
-            check(lib().mdl_cgconv_assemble_grads(ptr(dwn), ptr(dwe), ptr(db), C, G, ptr(dW_f), ptr(dW_s), ptr(db_f), ptr(db_s),
-                                                  stream()), "mdl_cgconv_assemble_grads")
-            return dx, None, dW_f.to(ctx.wdtypes[0]), db_f, dW_s.to(ctx.wdtypes[1]), db_s, None, None, None, None, None
-        Wn = torch.cat([wf32[:, :C], ws32[:, :C], wf32[:, C:2 * C], ws32[:, C:2 * C]], dim=0)      # [4C, C]
-        rt = r_tgt.view(N, 2, Cp)[:, :, :C]                                                        # library GEMMs
-        rs = r_src.view(N, 2, Cp)[:, :, :C]
-        cd = torch.float32 if dt == _lib.MDL_F32 else torch.bfloat16
-        R = torch.cat([rt[:, 0], rt[:, 1], rs[:, 0], rs[:, 1]], dim=1).to(cd)                      # [N, 4C]
-        dx = torch.addmm(g, R, Wn.to(cd))
-        dWn = torch.mm(R.t(), x).float()                                                           # [4C, C]
-        dwe_f, dwe_s = dwe[:C, :G], dwe[Cp:Cp + C, :G]
-        dW_f = torch.cat([dWn[0:C], dWn[2 * C:3 * C], dwe_f], dim=1).to(ctx.wdtypes[0])
-        dW_s = torch.cat([dWn[C:2 * C], dWn[3 * C:4 * C], dwe_s], dim=1).to(ctx.wdtypes[1])
-        db_f = db[:C].clone() if ctx.has_bias[0] else None
-        db_s = db[Cp:Cp + C].clone() if ctx.has_bias[1] else None
-        return dx, None, dW_f, db_f, dW_s, db_s, None, None, None, None, None
+            dW_f, db_f, dW_s, db_s = _assemble_grads(ctx, dwn, dwe, db, C, G, x.device, timed=False)
+        else:
+            Wn = torch.cat([wf32[:, :C], ws32[:, :C], wf32[:, C:2 * C], ws32[:, C:2 * C]], dim=0)      # [4C, C]
+            rt = r_tgt.view(N, 2, Cp)[:, :, :C]                                                        # library GEMMs
+            rs = r_src.view(N, 2, Cp)[:, :, :C]
+            cd = torch.float32 if dt == _lib.MDL_F32 else torch.bfloat16
+            R = torch.cat([rt[:, 0], rt[:, 1], rs[:, 0], rs[:, 1]], dim=1).to(cd)                      # [N, 4C]
+            dx = torch.addmm(g, R, Wn.to(cd))
+            dWn = torch.mm(R.t(), x).float()                                                           # [4C, C]
+            dW_f = torch.cat([dWn[0:C], dWn[2 * C:3 * C], dwe[:C, :G]], dim=1)
+            dW_s = torch.cat([dWn[C:2 * C], dWn[3 * C:4 * C], dwe[Cp:Cp + C, :G]], dim=1)
+            db_f = db[:C].clone() if ctx.has_bias[0] else None
+            db_s = db[Cp:Cp + C].clone() if ctx.has_bias[1] else None
+        return dx, None, dW_f.to(ctx.wdtypes[0]), db_f, dW_s.to(ctx.wdtypes[1]), db_s, None, None, None, None, None
+
+
+def _node_weights(ctx, C, Cp, dtype, device, wf32, ws32):
+    """Wn^T [C, 4 Cp] (columns f_tgt | s_tgt | f_src | s_src, zero-padded to Cp each) of the backward's node-level products:
+    what the forward (or cgconv_prepack) packed with its own weights, or packed now"""
+    wn_t, ctx.wn_t = ctx.wn_t, None
+    if wn_t is None:
+        wn_t = torch.empty((C, 4 * Cp), dtype=dtype, device=device)
+        check(lib().mdl_cgconv_pack_node_weights(ptr(wf32), ptr(ws32), C, wf32.shape[1] - 2 * C, ptr(wn_t), dtype_code(wn_t), stream()),
+              "mdl_cgconv_pack_node_weights")
+    return wn_t
+
+
+def _assemble_grads(ctx, dwn, dwe, db, C, G, device, timed):
+    """(dW_f, db_f, dW_s, db_s) fp32 from the kernels' staging buffers (mdl_cgconv_assemble_grads)"""
+    dW_f = torch.empty((C, 2 * C + G), dtype=torch.float32, device=device)
+    dW_s = torch.empty_like(dW_f)
+    db_f = torch.empty(C, dtype=torch.float32, device=device) if ctx.has_bias[0] else None
+    db_s = torch.empty(C, dtype=torch.float32, device=device) if ctx.has_bias[1] else None
+    launch = lambda: lib().mdl_cgconv_assemble_grads(ptr(dwn), ptr(dwe), ptr(db), C, G, ptr(dW_f), ptr(dW_s), ptr(db_f), ptr(db_s), stream())
+    check(_launch_timed("bwd_grads", launch) if timed else launch(), "mdl_cgconv_assemble_grads")
+    return dW_f, db_f, dW_s, db_s
 
 
 def cgconv_prepack(convs, x_dtype, device, want_node=True):
@@ -970,12 +974,36 @@ def cgconv(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr="mean", csr=None, 
         csr = csr_for(edge_index, x.shape[0])
     if dist is None:
         return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], bn_stats, packed, split)
+    d_norm, offsets, coeff = _check_dist("cgconv", dist, edge_attr, "edge_attr")
+    return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], bn_stats, packed, split, d_norm,
+                           (offsets.float(), float(coeff)))
+
+
+def _check_dist(name, dist, edge_attr, what):
+    """dist = (d_norm, offsets, coeff) of cgconv / cfconv, validated against the edge features (`what`: their name in the message)"""
     d_norm, offsets, coeff = dist
     require_hip(d_norm, offsets)
     if d_norm.dtype != torch.float32 or d_norm.numel() != edge_attr.shape[0] or offsets.numel() != edge_attr.shape[1]:
-        raise MdlError("cgconv: dist = (d_norm [E] float32, offsets [G], coeff) must match edge_attr %s" % (tuple(edge_attr.shape),))
-    return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], bn_stats, packed, split, d_norm,
-                           (offsets.float(), float(coeff)))
+        raise MdlError("%s: dist = (d_norm [E] float32, offsets [G], coeff) must match %s %s" % (name, what, tuple(edge_attr.shape)))
+    return d_norm, offsets, coeff
+
+
+def _dist_grad_inputs(name, x, edge_index, d_norm, csr, start, stop, resolution, width, edge_attr, out):
+    """What the two *_dist_grad functions share: (csr, offsets [G], d_norm in CSR order, edge features in CSR order and x's dtype —
+    the caller's edge_attr, or the expansion of d_norm)."""
+    if csr is None:
+        csr = csr_for(edge_index, x.shape[0])
+    if d_norm.dtype != torch.float32 or d_norm.numel() != csr.E or csr.N != x.shape[0]:
+        raise MdlError("%s: d_norm must be [E] float32 over the CSR's %d edges" % (name, csr.E))
+    if out is not None and csr.eperm is not None:
+        raise MdlError("%s: out= needs an edge list in CSR (target-sorted) order" % name)
+    offsets = rbf_offsets(start, stop, resolution, x.device)
+    d_sorted = _sort_edges(d_norm, csr).contiguous()
+    if edge_attr is None:
+        ea = rbf_expand(d_sorted.detach(), start, stop, resolution, width, out_dtype=x.dtype, offsets=offsets)
+    else:
+        ea = csr.sorted_attr(edge_attr.detach().contiguous())
+    return csr, offsets, d_sorted, ea
 
 
 def _bwd_edge_launch(x, ea_sorted, csr, wpack, bpack, g, aggr, C, G, de=None, d_sorted=None, offsets=None, coeff=0.0, scale=1.0, dd=None):
@@ -986,8 +1014,9 @@ def _bwd_edge_launch(x, ea_sorted, csr, wpack, bpack, g, aggr, C, G, de=None, d_
         "mdl_cgconv_bwd_edge")
 
 
-def _plain_pack(wf32, bf32, ws32, bs32, C, G, dt, device):
-    wpack = torch.empty(lib().mdl_cgconv_wpack_bytes(C, G, dt), dtype=torch.uint8, device=device)
+def _plain_pack(wf32, bf32, ws32, bs32, C, G, dt, device, nbytes=None):
+    """(wpack, bpack) of one layer by mdl_cgconv_pack_weights; nbytes: mdl_cgconv_wpack_bytes(C, G, dt) where the caller has it"""
+    wpack = torch.empty(lib().mdl_cgconv_wpack_bytes(C, G, dt) if nbytes is None else nbytes, dtype=torch.uint8, device=device)
     bpack = torch.empty(2 * _rup(C, 32), dtype=torch.float32, device=device)
     check(lib().mdl_cgconv_pack_weights(ptr(wf32), ptr(bf32), ptr(ws32), ptr(bs32), C, G, ptr(wpack), ptr(bpack), dt, stream()),
           "mdl_cgconv_pack_weights")
@@ -1014,7 +1043,7 @@ def _cgconv_edge_grads(ctx, g, need_de, need_dd):
     if x.shape[1] != C:
         x = x[:, :C].contiguous()                         # a padded layer: the edge-gradient kernel runs at the true width
     g = g.contiguous()
-    if getattr(ctx, "split", 0):                          # bf16x3 layer: exact fp32 form on plainly packed weights
+    if ctx.split:                                         # bf16x3 layer: exact fp32 form on plainly packed weights
         wpack, bpack = _plain_pack(wf32, ctx.bias32[0], ws32, ctx.bias32[1], C, G, dt, x.device)
     de = dd = None
     if need_de:
@@ -1023,7 +1052,7 @@ def _cgconv_edge_grads(ctx, g, need_de, need_dd):
         de = _unsort_edges(de, csr)
     if need_dd:
         d_norm, offsets = saved[6], saved[7]
-        d_sorted = d_norm if csr.eperm is None else d_norm.index_select(0, csr.eperm.long())
+        d_sorted = _sort_edges(d_norm, csr)
         dd = torch.zeros(E, dtype=torch.float32, device=x.device)
         _bwd_edge_launch(x, edge_attr, csr, wpack, bpack, g, ctx.aggr, C, G, d_sorted=d_sorted, offsets=offsets, coeff=ctx.rbf_coeff, dd=dd)
         dd = _unsort_edges(dd, csr)
@@ -1041,27 +1070,13 @@ def cgconv_dist_grad(x, edge_index, d_norm, w_f, b_f, w_s, b_s, grad_out, aggr="
     if aggr not in ("mean", "add", "sum"):
         raise MdlError("cgconv_dist_grad: aggr must be mean or add")
     require_hip(x, d_norm, w_f, w_s, grad_out)
-    if csr is None:
-        csr = csr_for(edge_index, x.shape[0])
     with torch.no_grad():
-        N, C = x.shape
-        G, E = int(resolution), d_norm.numel()
-        if d_norm.dtype != torch.float32 or E != csr.E or csr.N != N:
-            raise MdlError("cgconv_dist_grad: d_norm must be [E] float32 over the CSR's %d edges" % csr.E)
-        if out is not None and csr.eperm is not None:
-            raise MdlError("cgconv_dist_grad: out= needs an edge list in CSR (target-sorted) order")
-        dt = dtype_code(x)
+        C, G, dt = x.shape[1], int(resolution), dtype_code(x)
         if lib().mdl_cgconv_wpack_bytes(C, G, dt) == 0:
             raise MdlError("cgconv_dist_grad: unsupported C=%d G=%d" % (C, G))
-        offsets = rbf_offsets(start, stop, G, x.device)
-        d_sorted = (d_norm if csr.eperm is None else d_norm.index_select(0, csr.eperm.long())).contiguous()
-        if edge_attr is None:
-            ea = rbf_expand(d_sorted.detach(), start, stop, G, width, out_dtype=x.dtype, offsets=offsets)
-        else:
-            ea = csr.sorted_attr(edge_attr.detach().contiguous())
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()
-        wpack, bpack = _plain_pack(f32(w_f), f32(b_f), f32(w_s), f32(b_s), C, G, dt, x.device)
-        dd = out if out is not None else torch.zeros(E, dtype=torch.float32, device=x.device)
+        csr, offsets, d_sorted, ea = _dist_grad_inputs("cgconv_dist_grad", x, edge_index, d_norm, csr, start, stop, G, width, edge_attr, out)
+        wpack, bpack = _plain_pack(_f32c(w_f), _f32c(b_f), _f32c(w_s), _f32c(b_s), C, G, dt, x.device)
+        dd = out if out is not None else torch.zeros(csr.E, dtype=torch.float32, device=x.device)
         _bwd_edge_launch(x.detach().contiguous(), ea, csr, wpack, bpack, grad_out.detach().to(x.dtype).contiguous(), _lib.REDUCE[aggr], C, G,
                          d_sorted=d_sorted, offsets=offsets, coeff=rbf_coeff(start, stop, width), scale=scale, dd=dd)
         return dd if out is not None else _unsort_edges(dd, csr)
@@ -1096,8 +1111,7 @@ def cgconv_bn(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr, csr, bn_weight
     C = x.shape[1]
     R = lib().mdl_bn_sums_rows()
     buf = _zeros_step((R + 3, C), x.device)                  # sums (copies + totals) | shift row | save (mean, invstd)
-    y = cgconv(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr, csr=csr,
-               bn_stats=(buf, None if shift is None else shift.detach().float().contiguous()), packed=packed)
+    y = cgconv(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr, csr=csr, bn_stats=(buf, _f32c(shift)), packed=packed)
     return _BatchNormTrain.apply(y, bn_weight, bn_bias, running_mean, running_var, eps, momentum, buf)
 
 
@@ -1245,18 +1259,44 @@ def cfconv_fused(rbf, cut, h, csr, lin_a, lin_b, want_acts):
     F, G = h.shape[1], rbf.shape[1]
     E, N = csr.E, csr.N
     dev = h.device
-    wpack = torch.empty(lib().mdl_cfconv_wpack_bytes(), dtype=torch.uint8, device=dev)
-    check(lib().mdl_cfconv_pack_weights(ptr(lin_a.weight), ptr(lin_a.bias), ptr(lin_b.weight), ptr(lin_b.bias), F, G, ptr(wpack),
-                                        stream()), "mdl_cfconv_pack_weights")
+    wpack = _cfconv_pack(lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias, F, G, dev)
     out = torch.empty((N, F), dtype=h.dtype, device=dev)
     a1 = torch.empty((E, F), dtype=h.dtype, device=dev) if want_acts else None
     w = torch.empty((E, F), dtype=h.dtype, device=dev) if want_acts else None
     h = h.contiguous()
-    cut = cut.float().contiguous()
-    check(_launch_timed("cfconv_fwd", lambda: lib().mdl_cfconv_fwd(
-        ptr(rbf), ptr(cut), ptr(h), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(out), ptr(a1), ptr(w), N, E, F, G,
-        dtype_code(h), stream())), "mdl_cfconv_fwd")
+    _cfconv_fwd_launch("cfconv_fwd", rbf, cut.float().contiguous(), h, csr.rowptr, csr.src, csr.tgt, wpack, N, E, out, a1, w)
     return out, a1, w
+
+
+def _cfconv_pack(w1, b1, w2, b2, F, G, device):
+    """the filter network's weights (dense fp32 rows) in the layout of the CFConv kernels"""
+    wpack = torch.empty(lib().mdl_cfconv_wpack_bytes(), dtype=torch.uint8, device=device)
+    check(lib().mdl_cfconv_pack_weights(ptr(w1), ptr(b1), ptr(w2), ptr(b2), F, G, ptr(wpack), stream()), "mdl_cfconv_pack_weights")
+    return wpack
+
+
+def _cfconv_fwd_launch(key, rbf, cut, x, rowptr, src, tgt, wpack, N, E, out, a1=None, w=None):
+    """mdl_cfconv_fwd: out[i] = sum over row i of x[src] * W(rbf) * cut.  key "cfconv_fwd": the forward on the by-target CSR
+    (a1, w: the per-edge activations, where wanted); "cfconv_bwd_h": the same kernel on the by-source CSR with x = grad_out
+    and (rbf, cut) in by-source order, which is dh."""
+    F, G = x.shape[1], rbf.shape[1]
+    check(_launch_timed(key, lambda: lib().mdl_cfconv_fwd(
+        ptr(rbf), ptr(cut), ptr(x), ptr(rowptr), ptr(src), ptr(tgt), ptr(wpack), ptr(out), ptr(a1), ptr(w), N, E, F, G,
+        dtype_code(out), stream())), "mdl_cfconv_fwd" if key == "cfconv_fwd" else "mdl_cfconv_fwd(T)")
+
+
+def _cfconv_param_grads(rbf, cut, h, g, csr, wpack, has_b):
+    """(dw1, db1, dw2, db2) of the filter network by mdl_cfconv_bwd_w (the filter is recomputed): fp32 views of one buffer"""
+    F, G = h.shape[1], rbf.shape[1]
+    buf = torch.zeros(F * G + F * F + 2 * F, dtype=torch.float32, device=h.device)    # (not the step arena: autograd may adopt these views as .grad)
+    dw1, dw2 = buf[:F * G].view(F, G), buf[F * G:F * G + F * F].view(F, F)
+    db1 = buf[F * G + F * F:F * G + F * F + F] if has_b[0] else None
+    db2 = buf[F * G + F * F + F:] if has_b[1] else None
+    scratch = torch.empty(lib().mdl_cfconv_bwd_w_scratch_bytes(), dtype=torch.uint8, device=h.device)
+    check(_launch_timed("cfconv_bwd_w", lambda: lib().mdl_cfconv_bwd_w(
+        ptr(rbf), ptr(cut), ptr(h), ptr(g), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(dw1), ptr(db1),
+        ptr(dw2), ptr(db2), ptr(scratch), csr.N, csr.E, F, G, dtype_code(h) | _dflag(), stream())), "mdl_cfconv_bwd_w")
+    return dw1, db1, dw2, db2
 
 
 class BySourceAttrs:
@@ -1277,56 +1317,9 @@ class BySourceAttrs:
         return self._v
 
 
-class _CFConvRecompute(torch.autograd.Function):
-    """out = CFConv aggregation (mdl_cfconv_fwd, nothing stored per edge); backward: dh by the same kernel on the by-source CSR,
-    the filter network's parameter gradients by mdl_cfconv_bwd_w (csrc/cfconv_bwd.hip) — the filter is recomputed in both."""
-
-    @staticmethod
-    def forward(ctx, rbf, cut, h, w1, b1, w2, b2, csr, cache):
-        require_hip(rbf, h)
-        F, G = h.shape[1], rbf.shape[1]
-        dev = h.device
-        wpack = torch.empty(lib().mdl_cfconv_wpack_bytes(), dtype=torch.uint8, device=dev)
-        check(lib().mdl_cfconv_pack_weights(ptr(w1), ptr(b1), ptr(w2), ptr(b2), F, G, ptr(wpack), stream()), "mdl_cfconv_pack_weights")
-        out = torch.empty((csr.N, F), dtype=h.dtype, device=dev)
-        h = h.contiguous()
-        cut = cut.float().contiguous()
-        check(_launch_timed("cfconv_fwd", lambda: lib().mdl_cfconv_fwd(
-            ptr(rbf), ptr(cut), ptr(h), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(out), None, None, csr.N, csr.E,
-            F, G, dtype_code(h), stream())), "mdl_cfconv_fwd")
-        ctx.csr, ctx.cache, ctx.has_b = csr, cache, (b1 is not None, b2 is not None)
-        ctx.save_for_backward(rbf, cut, h, wpack)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        rbf, cut, h, wpack = ctx.saved_tensors
-        csr = ctx.csr
-        N, E, F, G = csr.N, csr.E, h.shape[1], rbf.shape[1]
-        g = g.contiguous()
-        dh = dw1 = db1 = dw2 = db2 = None
-        if ctx.needs_input_grad[2]:
-            rowptr_s, col_s, eid_s, src_sorted = csr.transposed()
-            rbf_s, cut_s = (ctx.cache if ctx.cache is not None else BySourceAttrs()).get(rbf, cut, eid_s)
-            dh = torch.empty_like(h)
-            check(_launch_timed("cfconv_bwd_h", lambda: lib().mdl_cfconv_fwd(
-                ptr(rbf_s), ptr(cut_s), ptr(g), ptr(rowptr_s), ptr(col_s), ptr(src_sorted), ptr(wpack), ptr(dh), None, None, N, E, F, G,
-                dtype_code(h), stream())), "mdl_cfconv_fwd(T)")
-        if ctx.needs_input_grad[3] or ctx.needs_input_grad[5]:
-            buf = torch.zeros(F * G + F * F + 2 * F, dtype=torch.float32, device=h.device)    # (not the step arena: autograd may adopt these views as .grad)
-            dw1, dw2 = buf[:F * G].view(F, G), buf[F * G:F * G + F * F].view(F, F)
-            db1 = buf[F * G + F * F:F * G + F * F + F] if ctx.has_b[0] else None
-            db2 = buf[F * G + F * F + F:] if ctx.has_b[1] else None
-            scratch = torch.empty(lib().mdl_cfconv_bwd_w_scratch_bytes(), dtype=torch.uint8, device=h.device)
-            check(_launch_timed("cfconv_bwd_w", lambda: lib().mdl_cfconv_bwd_w(
-                ptr(rbf), ptr(cut), ptr(h), ptr(g), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(dw1), ptr(db1),
-                ptr(dw2), ptr(db2), ptr(scratch), N, E, F, G, dtype_code(h) | _dflag(), stream())), "mdl_cfconv_bwd_w")
-        return None, None, dh, dw1, db1, dw2, db2, None, None
-
-
 def cfconv_recompute(rbf, cut, h, csr, lin_a, lin_b, cache=None):
     """K4 + K4b: the CFConv aggregation as ONE autograd node that stores nothing per edge (see cfconv_fused_ok for the shapes)."""
-    return _CFConvRecompute.apply(rbf, cut, h, lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias, csr, cache)
+    return _CFConv.apply(rbf, cut, h, lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias, csr, None, None, cache)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1362,40 +1355,38 @@ def _sort_edges(t, csr):
 
 
 def _filter_f32(rbf, w1, b1, w2, b2):
-    a = torch.nn.functional.softplus(torch.nn.functional.linear(rbf, w1, b1)) - 0.6931471805599453
+    a = torch.nn.functional.softplus(torch.nn.functional.linear(rbf, w1, b1)) - _LN2
     return torch.nn.functional.linear(a, w2, b2)
 
 
-class _CFConvEdge(torch.autograd.Function):
-    """The CFConv aggregation as ONE autograd node that is also differentiable in its per-edge inputs (first order).
-    forward: bf16 = mdl_cfconv_fwd without activations; fp32 = the filter network + mdl_gather_mul_reduce.  backward: dh as
-    the training path forms it, the parameter gradients only for parameters that need them, and K4d for the edge inputs: dcut
-    for the cutoff, the distance epilogue for d_norm (dist given), the general epilogue for rbf."""
+class _CFConv(torch.autograd.Function):
+    """The CFConv aggregation as ONE autograd node that stores nothing per edge and is differentiable (first order) in h, the
+    filter network's parameters and the per-edge inputs.
+    forward: bf16 = mdl_cfconv_fwd without activations; fp32 = the filter network + mdl_gather_mul_reduce.  backward: dh by the
+    same kernel on the by-source CSR (cache: the model's BySourceAttrs, shared by its blocks), the parameter gradients by
+    mdl_cfconv_bwd_w (csrc/cfconv_bwd.hip) — the filter is recomputed in both —, and K4d for the edge inputs that ask: dcut for
+    the cutoff, the distance epilogue for d_norm (dist given), the general epilogue for rbf.
+    On the training path (cfconv_recompute: bf16, CSR-ordered edges, dense fp32 weights, no gradient on rbf / cut) every
+    conversion of the forward is an identity: the launches are the packing, the forward, dh and mdl_cfconv_bwd_w."""
 
     @staticmethod
-    def forward(ctx, rbf, cut, h, w1, b1, w2, b2, csr, d_norm, meta):
+    def forward(ctx, rbf, cut, h, w1, b1, w2, b2, csr, d_norm, meta, cache):
         require_hip(rbf, h, cut)
         F, G = h.shape[1], rbf.shape[1]
-        dev = h.device
         bf = h.dtype == torch.bfloat16
+        w1f, b1f, w2f, b2f = _f32c(w1), _f32c(b1), _f32c(w2), _f32c(b2)
+        wpack = _cfconv_pack(w1f, b1f, w2f, b2f, F, G, h.device) if bf else None
+        out = torch.empty((csr.N, F), dtype=h.dtype, device=h.device)
         h = h.contiguous()
         rbf_s = csr.sorted_attr(rbf.contiguous())
         cut_s = _sort_edges(cut.float(), csr).contiguous()
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()
-        w1f, b1f, w2f, b2f = f32(w1), f32(b1), f32(w2), f32(b2)
-        out = torch.empty((csr.N, F), dtype=h.dtype, device=dev)
-        wpack = None
         if bf:
-            wpack = torch.empty(lib().mdl_cfconv_wpack_bytes(), dtype=torch.uint8, device=dev)
-            check(lib().mdl_cfconv_pack_weights(ptr(w1f), ptr(b1f), ptr(w2f), ptr(b2f), F, G, ptr(wpack), stream()), "mdl_cfconv_pack_weights")
-            check(_launch_timed("cfconv_fwd", lambda: lib().mdl_cfconv_fwd(
-                ptr(rbf_s), ptr(cut_s), ptr(h), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(out), None, None, csr.N,
-                csr.E, F, G, dtype_code(h), stream())), "mdl_cfconv_fwd")
+            _cfconv_fwd_launch("cfconv_fwd", rbf_s, cut_s, h, csr.rowptr, csr.src, csr.tgt, wpack, csr.N, csr.E, out)
         else:
             w_s = _filter_f32(rbf_s, w1f, b1f, w2f, b2f).contiguous()
             check(lib().mdl_gather_mul_reduce(ptr(h), ptr(w_s), ptr(cut_s), ptr(csr.rowptr), ptr(csr.src), None, ptr(out), csr.N, F,
                                               _lib.MDL_SUM, dtype_code(h), stream()), "mdl_gather_mul_reduce")
-        ctx.csr, ctx.meta, ctx.has_b = csr, meta, (b1 is not None, b2 is not None)
+        ctx.csr, ctx.meta, ctx.cache, ctx.has_b = csr, meta, cache, (b1 is not None, b2 is not None)
         ctx.save_for_backward(rbf_s, cut_s, h, wpack, w1f, b1f, w2f, b2f, d_norm)
         return out
 
@@ -1415,29 +1406,19 @@ class _CFConvEdge(torch.autograd.Function):
             if csr.eperm is None:
                 pos_s = eid_s
             else:
-                inv = torch.empty_like(csr.eperm)
-                inv[csr.eperm.long()] = torch.arange(E, dtype=csr.eperm.dtype, device=h.device)
-                pos_s = inv.index_select(0, eid_s.long())
+                inv = _unsort_edges(torch.arange(E, dtype=csr.eperm.dtype, device=h.device), csr)
+                pos_s = inv.index_select(0, eid_s.long()).contiguous()
             dh = torch.empty_like(h)
             if bf:
-                rbf_t, cut_t = BySourceAttrs().get(rbf_s, cut_s, pos_s.contiguous())
-                check(_launch_timed("cfconv_bwd_h", lambda: lib().mdl_cfconv_fwd(
-                    ptr(rbf_t), ptr(cut_t), ptr(g), ptr(rowptr_s), ptr(col_s), ptr(src_sorted), ptr(wpack), ptr(dh), None, None, N, E, F,
-                    G, dtype_code(h), stream())), "mdl_cfconv_fwd(T)")
+                rbf_t, cut_t = (ctx.cache if ctx.cache is not None else BySourceAttrs()).get(rbf_s, cut_s, pos_s)
+                _cfconv_fwd_launch("cfconv_bwd_h", rbf_t, cut_t, g, rowptr_s, col_s, src_sorted, wpack, N, E, dh)
             else:
                 w_s = _filter_f32(rbf_s, w1f, b1f, w2f, b2f).contiguous()
-                check(lib().mdl_gather_mul_reduce(ptr(g), ptr(w_s), ptr(cut_s), ptr(rowptr_s), ptr(col_s), ptr(pos_s.contiguous()), ptr(dh),
+                check(lib().mdl_gather_mul_reduce(ptr(g), ptr(w_s), ptr(cut_s), ptr(rowptr_s), ptr(col_s), ptr(pos_s), ptr(dh),
                                                   N, F, _lib.MDL_SUM, dtype_code(h), stream()), "mdl_gather_mul_reduce(T)")
         if need[3] or need[4] or need[5] or need[6]:
             if bf:
-                buf = torch.zeros(F * G + F * F + 2 * F, dtype=torch.float32, device=h.device)
-                dw1, dw2 = buf[:F * G].view(F, G), buf[F * G:F * G + F * F].view(F, F)
-                db1 = buf[F * G + F * F:F * G + F * F + F] if ctx.has_b[0] else None
-                db2 = buf[F * G + F * F + F:] if ctx.has_b[1] else None
-                scratch = torch.empty(lib().mdl_cfconv_bwd_w_scratch_bytes(), dtype=torch.uint8, device=h.device)
-                check(_launch_timed("cfconv_bwd_w", lambda: lib().mdl_cfconv_bwd_w(
-                    ptr(rbf_s), ptr(cut_s), ptr(h), ptr(g), ptr(csr.rowptr), ptr(csr.src), ptr(csr.tgt), ptr(wpack), ptr(dw1), ptr(db1),
-                    ptr(dw2), ptr(db2), ptr(scratch), N, E, F, G, dtype_code(h) | _dflag(), stream())), "mdl_cfconv_bwd_w")
+                dw1, db1, dw2, db2 = _cfconv_param_grads(rbf_s, cut_s, h, g, csr, wpack, ctx.has_b)
             else:
                 # fp32: the filter gradient by mdl_edge_mul, the two dense layers' parameter gradients by the library
                 dwf = torch.empty((E, F), dtype=h.dtype, device=h.device)
@@ -1446,7 +1427,7 @@ class _CFConvEdge(torch.autograd.Function):
                 if csr.partial:
                     dwf[int(csr.rowptr[-1]):] = 0
                 pre = torch.nn.functional.linear(rbf_s, w1f, b1f)
-                a = torch.nn.functional.softplus(pre) - 0.6931471805599453
+                a = torch.nn.functional.softplus(pre) - _LN2
                 dw2, db2 = dwf.t() @ a, (dwf.sum(0) if ctx.has_b[1] else None)
                 da = (dwf @ w2f) * torch.sigmoid(pre)
                 dw1, db1 = da.t() @ rbf_s, (da.sum(0) if ctx.has_b[0] else None)
@@ -1468,7 +1449,7 @@ class _CFConvEdge(torch.autograd.Function):
                 _cfconv_bwd_edge_launch(rbf_s, cut_s, h, g, csr, wpack, w1f, b1f, w2f, b2f, dcut=dcut)
             if dcut is not None:
                 dcut = _unsort_edges(dcut, csr)
-        return drbf, dcut, dh, dw1, db1, dw2, db2, None, ddn, None
+        return drbf, dcut, dh, dw1, db1, dw2, db2, None, ddn, None, None
 
 
 def cfconv(rbf, cut, h, csr, lin_a, lin_b, dist=None):
@@ -1482,14 +1463,11 @@ def cfconv(rbf, cut, h, csr, lin_a, lin_b, dist=None):
         raise MdlError("cfconv: unsupported shape F=%d G=%d %s (mdl_cfconv_bwd_edge_supported)" % (h.shape[1], rbf.shape[1], h.dtype))
     if rbf.shape[0] != csr.E:
         raise MdlError("cfconv: rbf must have one row per edge of the CSR")
+    args = (cut, h, lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias, csr)
     if dist is None:
-        return _CFConvEdge.apply(rbf, cut, h, lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias, csr, None, None)
-    d_norm, offsets, coeff = dist
-    require_hip(d_norm, offsets)
-    if d_norm.dtype != torch.float32 or d_norm.numel() != rbf.shape[0] or offsets.numel() != rbf.shape[1]:
-        raise MdlError("cfconv: dist = (d_norm [E] float32, offsets [G], coeff) must match rbf %s" % (tuple(rbf.shape),))
-    return _CFConvEdge.apply(rbf.detach(), cut, h, lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias, csr, d_norm,
-                             (offsets.float().contiguous(), float(coeff)))
+        return _CFConv.apply(rbf, *args, None, None, None)
+    d_norm, offsets, coeff = _check_dist("cfconv", dist, rbf, "rbf")
+    return _CFConv.apply(rbf.detach(), *args, d_norm, (offsets.float().contiguous(), float(coeff)), None)
 
 
 def cfconv_dist_grad(h, edge_index, d_norm, cut, w1, b1, w2, b2, grad_out, csr=None, start=0.0, stop=1.0, resolution=50, width=0.2,
@@ -1501,30 +1479,14 @@ def cfconv_dist_grad(h, edge_index, d_norm, cut, w1, b1, w2, b2, grad_out, csr=N
     factor; `out` ([E] fp32, CSR-ordered edge lists only) is added into instead, so that the blocks of a model accumulate in one
     buffer.  No atomics: bitwise repeatable.  No gradient flows through this call itself."""
     require_hip(h, d_norm, w1, w2, grad_out, cut)
-    if csr is None:
-        csr = csr_for(edge_index, h.shape[0])
     with torch.no_grad():
-        N, F = h.shape
-        G, E = int(resolution), d_norm.numel()
-        if d_norm.dtype != torch.float32 or E != csr.E or csr.N != N:
-            raise MdlError("cfconv_dist_grad: d_norm must be [E] float32 over the CSR's %d edges" % csr.E)
-        if out is not None and csr.eperm is not None:
-            raise MdlError("cfconv_dist_grad: out= needs an edge list in CSR (target-sorted) order")
-        dt = dtype_code(h)
-        if not lib().mdl_cfconv_bwd_edge_supported(F, G, dt):
+        F, G = h.shape[1], int(resolution)
+        if not lib().mdl_cfconv_bwd_edge_supported(F, G, dtype_code(h)):
             raise MdlError("cfconv_dist_grad: unsupported F=%d G=%d" % (F, G))
-        offsets = rbf_offsets(start, stop, G, h.device)
-        d_sorted = _sort_edges(d_norm, csr).contiguous()
-        if edge_attr is None:
-            ea = rbf_expand(d_sorted.detach(), start, stop, G, width, out_dtype=h.dtype, offsets=offsets)
-        else:
-            ea = csr.sorted_attr(edge_attr.detach().contiguous())
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()
-        w1f, b1f, w2f, b2f = f32(w1), f32(b1), f32(w2), f32(b2)
-        wpack = None
-        if h.dtype == torch.bfloat16:
-            wpack = torch.empty(lib().mdl_cfconv_wpack_bytes(), dtype=torch.uint8, device=h.device)
-            check(lib().mdl_cfconv_pack_weights(ptr(w1f), ptr(b1f), ptr(w2f), ptr(b2f), F, G, ptr(wpack), stream()), "mdl_cfconv_pack_weights")
+        csr, offsets, d_sorted, ea = _dist_grad_inputs("cfconv_dist_grad", h, edge_index, d_norm, csr, start, stop, G, width, edge_attr, out)
+        E = csr.E
+        w1f, b1f, w2f, b2f = _f32c(w1), _f32c(b1), _f32c(w2), _f32c(b2)
+        wpack = _cfconv_pack(w1f, b1f, w2f, b2f, F, G, h.device) if h.dtype == torch.bfloat16 else None
         dd = out if out is not None else torch.zeros(E, dtype=torch.float32, device=h.device)
         dcut = torch.zeros(E, dtype=torch.float32, device=h.device) if want_dcut else None
         _cfconv_bwd_edge_launch(ea, _sort_edges(cut.detach().float(), csr).contiguous(), h.detach().contiguous(),
@@ -1788,7 +1750,7 @@ class _LinearActTN(torch.autograd.Function):
             out = pre.view_as(pre)
         else:
             out = torch.empty((N, M), dtype=x.dtype, device=x.device)
-            check(lib().mdl_linear_act(ptr(x), ptr(w), ptr(b), ptr(out), N, K, M, {"relu": 1, "ssp": 2}.get(act, 0), dtype_code(x),
+            check(lib().mdl_linear_act(ptr(x), ptr(w), ptr(b), ptr(out), N, K, M, _ACT_CODE.get(act, 0), dtype_code(x),
                                        stream()), "mdl_linear_act")
         ctx.save_for_backward(x, w, out if act in ("relu", "ssp") and not out_pre else None)
         ctx.wdtype, ctx.has_bias, ctx.shape, ctx.act = weight.dtype, bias is not None, tuple(weight.shape), act
@@ -1798,7 +1760,7 @@ class _LinearActTN(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, w, out = ctx.saved_tensors
-        code = 0 if ctx.out_pre else {"relu": 1, "ssp": 2}.get(ctx.act, 0)
+        code = 0 if ctx.out_pre else _ACT_CODE.get(ctx.act, 0)
         tail = (None, None, None, None, None, None)
         if _dense_bwd_ok(ctx, g, x, w, out if code else None):
             return _dense_bwd(ctx, g, x, w, (code, out) if code else None, xout=ctx.in_act) + tail
@@ -1817,7 +1779,7 @@ class _LinearActTN(torch.autograd.Function):
             if ctx.in_act == 1:
                 dx = torch.ops.aten.threshold_backward(dx, x, 0)
             else:
-                dx = (dx.float() * (1.0 - torch.exp(-(x.float() + 0.6931471805599453)))).to(dx.dtype)
+                dx = (dx.float() * (1.0 - torch.exp(-(x.float() + _LN2)))).to(dx.dtype)
         return (dx, dw, db) + tail
 
 
@@ -2008,13 +1970,13 @@ def linear_act(x, weight, bias, act, lowp=None, in_act=None, out_pre=False, pre=
     both layers first)."""
     if linear_act_fused_ok(x, weight, act):
         w_lp, b_lp = (lowp if lowp is not None and lowp[0].dtype == x.dtype else (None, None))
-        return _LinearActTN.apply(x, weight, bias, w_lp, b_lp, act, {"relu": 1, "ssp": 2}.get(in_act, 0), out_pre, pre)
+        return _LinearActTN.apply(x, weight, bias, w_lp, b_lp, act, _ACT_CODE.get(in_act, 0), out_pre, pre)
     assert not in_act and not out_pre and pre is None, "linear_act: activation hand-over on a layer that is not fused"
     y = linear(x, weight, bias, lowp)
     if act is None:
         return y
     if act == "ssp":
-        return torch.nn.functional.softplus(y) - 0.6931471805599453
+        return torch.nn.functional.softplus(y) - _LN2
     return getattr(torch.nn.functional, act)(y)
 
 
@@ -2264,8 +2226,7 @@ class _BatchNormTrain(torch.autograd.Function):
         # pre: [R + 3, C] buffer whose sums the PRODUCER of x has already formed about the shift in row R (cgconv_bn)
         buf = _zeros_step((R + 2, C), x.device) if pre is None else pre       # rows 0..R-1: sums (copies + totals) [| shift] | save
         sums, save = buf[:R], buf[-2:]
-        gw = None if weight is None else weight.detach().float().contiguous()
-        gb = None if bias is None else bias.detach().float().contiguous()
+        gw, gb = _f32c(weight), _f32c(bias)
         y = torch.empty_like(x)
         nd = _true_rows_for(N)
         # (statistics + apply as ONE launch for few rows was built and measured slower at the reference's batch size — 0.54 vs
@@ -2340,8 +2301,7 @@ class _LinearReluBN(torch.autograd.Function):
                 N, K, M, 1, dt, stream())), "mdl_linear_gather_act")
         else:
             check(lib().mdl_linear_act(ptr(x), ptr(w), ptr(b), ptr(y), N, K, M, 1, dt, stream()), "mdl_linear_act")
-        gw = None if bn_w is None else bn_w.detach().float().contiguous()
-        gb = None if bn_b is None else bn_b.detach().float().contiguous()
+        gw, gb = _f32c(bn_w), _f32c(bn_b)
         z = torch.empty_like(y)
         if not in_epilogue:
             check(lib().mdl_bn_stats_n(ptr(y), ptr(sums), N, M, ptr(nd), dt | _dflag(), stream()), "mdl_bn_stats")
