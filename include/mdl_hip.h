@@ -608,6 +608,25 @@ int mdl_cgconv_bwd_edge(const void* x, const void* edge_attr, const int32_t* row
                         int aggr, int dtype, void* de, const float* d_norm, const float* offsets, float coeff, float scale,
                         float* dd, mdlStream_t stream);
 
+/* ---- First-edge-layer distance gradient (csrc/linear_de.hip) ---------------------------------
+ * No reference counterpart (megnet.py:222-247 and mpnn.py:83-88 feed their first edge layer constant edge features; upstream
+ * autograd would go through an [E, G] input gradient).  For a dense layer y = act(W r(d) + b) that reads the Gaussian expansion
+ * r_k(d) = exp(coeff (d - offsets[k])^2), W [M, G]:
+ *     dd[e] (+)= scale * sum_k ( sum_c gp[e, c] W[c, k] ) * 2 coeff (d[e] - offsets[k]) exp(coeff (d[e] - offsets[k])^2)
+ *   act_y == NULL  gp = g: the gradient w.r.t. the layer's pre-activation (or a layer without activation);
+ *   act_y != NULL  gp = g * (act_y > 0): g is the gradient w.r.t. the ReLU output act_y, the mask is applied in the kernel.
+ * g / act_y: [E, M] row-major with leading dimensions ld_g / ld_y (>= M) in `dtype`; w: [M, G] row-major in `dtype` (fp32, or
+ * the bf16 copy the forward multiplies); d / offsets / coeff as in mdl_rbf_expand_bwd; dd: [E] fp32, written (accumulate == 0)
+ * or added into.  The exponential is recomputed from d and the [E, G] input gradient stays in registers: M s (+ M s with the
+ * mask) + 8 bytes per edge.  Purely per edge (no CSR, no order), one lane writes dd[e]: no atomics, bitwise repeatable; rows
+ * past E are never touched.  fp32: exact fp32 products; bf16: bf16 products with fp32 accumulation.  M in 1..256, G in 1..64,
+ * MDL_F32 / MDL_BF16 (mdl_linear_rbf_dist_grad_supported), else MDL_E_UNSUPP and the caller composes the layer's input gradient
+ * with mdl_rbf_expand_bwd.  E == 0 returns 0 without a launch. */
+int mdl_linear_rbf_dist_grad_supported(int M, int G, int dtype);
+int mdl_linear_rbf_dist_grad(const void* g, int64_t ld_g, const void* act_y, int64_t ld_y, const void* w, int dtype,
+                             const float* d, const float* offsets, float coeff, float scale, float* dd, int accumulate,
+                             int64_t E, int M, int G, mdlStream_t stream);
+
 /* ---- Edge geometry: distances of given edges as a function of the positions (csrc/edge_geom.hip) ----
  * No reference counterpart (the reference has no force path).  Structures packed as for mdl_graph_build; src / tgt: [E] int32
  * BATCH-GLOBAL node ids of edges src -> tgt inside one structure.

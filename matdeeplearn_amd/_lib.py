@@ -138,6 +138,8 @@ PROTOTYPES = {
     "mdl_graph_build": (_i32, [_vp] * 4 + [_i64, _i64, ctypes.c_double, _i32] + [_vp] * 5 + [_i64, _vp, _sz, _vp]),
     "mdl_rbf_expand_bwd": (_i32, [_vp, _i64, _i32, _vp, _vp, _f32, _vp, _i64, _i32, _vp]),
     "mdl_cgconv_bwd_edge": (_i32, [_vp] * 8 + [_i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _vp, _vp]),
+    "mdl_linear_rbf_dist_grad_supported": (_i32, [_i32, _i32, _i32]),
+    "mdl_linear_rbf_dist_grad": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _f32, _f32, _vp, _i32, _i64, _i32, _i32, _vp]),
     "mdl_edge_geometry_workspace_bytes": (_sz, [_i64]),
     "mdl_edge_geometry_fwd": (_i32, [_vp] * 4 + [_i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "mdl_edge_geometry_bwd": (_i32, [_vp] * 6 + [_i64, _i64, _vp, _vp]),

@@ -1,6 +1,6 @@
 """Forces from atomic positions: F = -dE/dpos through  positions -> minimum-image distances -> graph -> Gaussian expansion ->
-CGCNN or SchNet -> prediction, all of it on the HIP device.  The reference has no force path; this is the derivative chain of the model
-the reference defines (matdeeplearn/models/cgcnn.py) on the graphs it builds (matdeeplearn/process/process.py:258-305).
+CGCNN, SchNet, MEGNet or MPNN -> prediction, all of it on the HIP device.  The reference has no force path; this is the derivative
+chain of the models the reference defines (matdeeplearn/models/) on the graphs it builds (matdeeplearn/process/process.py:258-305).
 
 Chain, one public call (energy_and_forces):
   ops.build_graphs      neighbour lists — then HELD FIXED: forces are the derivative at fixed topology, as in every k-NN graph
@@ -12,6 +12,11 @@ Chain, one public call (energy_and_forces):
                         edge-feature gradient per layer and mdl_rbf_expand_bwd, for comparison)
   models.SchNet with ops.cfconv(dist=...): the same through csrc/cfconv_de.hip, plus the second route — the cosine cutoff of the
                         RAW distance scales every message, so edge_weight carries a gradient and every block returns dL/dcut
+  models.MEGNet / models.MPNN: the distance enters through one kind of layer only, a Linear(G -> M) + ReLU on the expansion —
+                        the first layer of MEGNet's e_embed_list[0] (once), the first layer of every NNConv's edge network
+                        (once per layer).  ops.rbf_linear_act puts a node behind that layer whose backward returns dL/dd from
+                        csrc/linear_de.hip; everything behind it (gathers, scatters, BatchNorm, nnconv_msg, the GRU gates) is
+                        differentiable in its inputs as it is
 No gradient w.r.t. the cell (stress) and no second derivatives (training on forces): both raise or are absent by construction."""
 import numpy as np
 import torch
@@ -50,34 +55,37 @@ def _node_features(numbers, out_deg, max_neighbors, dictionary, dev):
 
 def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, dictionary=None, output_index=None, fused=True,
                       routes=("expansion", "cutoff")):
-    """Prediction and forces F = -d(prediction)/d(positions) of a CGCNN or a SchNet.
+    """Prediction and forces F = -d(prediction)/d(positions) of a CGCNN, SchNet, MEGNet or MPNN.
 
-    model        a matdeeplearn_amd.models.CGCNN or .SchNet on a HIP device (GCN / MPNN / MEGNet raise MdlError).  Its CURRENT
+    model        a matdeeplearn_amd.models.CGCNN, .SchNet, .MEGNet or .MPNN on a HIP device (GCN raises MdlError).  Its CURRENT
                  mode is used.  eval() is the meaningful one: in training mode BatchNorm's batch statistics couple the graphs of
                  a batch (an atom would feel forces from other structures) and dropout makes the energy a random function.
     structs      a list of dict(positions, numbers, cell, pbc), or the packed arrays of process.graph.pack_structures
     dist_range   (min, max) of the TRAINING set's distance normalisation (GraphDataset.dist_range)
     radius, max_neighbors, dictionary   as process.from_structures
     output_index for a model with several outputs: the one to differentiate (default: the sum over the outputs)
-    fused        True: dL/dd from the fused distance epilogue of the edge-gradient kernel; False: through an [E, G] edge-feature
-                 gradient per layer (same result to rounding; for comparison)
+    fused        True: dL/dd from the fused distance epilogue of the edge-gradient kernel (MEGNet / MPNN: of the first edge
+                 layer, csrc/linear_de.hip); False: through an [E, G] edge-feature gradient per layer (same result to rounding;
+                 for comparison)
 
     routes       diagnostic (SchNet): which of the two ways the distance enters carries the derivative — "expansion" (the Gaussian
                  expansion that feeds the filter network) and / or "cutoff" (the cosine cutoff of the raw distance).  The default,
-                 both, is the force; one alone is that route's share (the two shares add up to the force).
+                 both, is the force; one alone is that route's share (the two shares add up to the force).  The other models
+                 have the expansion route only: without "expansion" their forces are zero.
 
     Returns (pred [B] or [B, out] fp32, forces [N, 3] fp32, node_ptr [B + 1] int64), device tensors; atom n of structure b is row
     node_ptr[b] + n.  The neighbour lists are built once from the given positions and HELD FIXED under the derivative; the image
     shifts and the cell are constants too (no stress).  Forces of a graph sum to zero up to fp32 rounding; with
     ops.deterministic() two calls return the same bits."""
-    from .models import CGCNN, SchNet
-    if not isinstance(model, (CGCNN, SchNet)):
-        raise ops.MdlError("energy_and_forces: forces are implemented for CGCNN and SchNet (got %s); the other models' edge paths "
-                           "lack the distance gradient (DESIGN.md)" % type(model).__name__)
+    from .models import CGCNN, MEGNet, MPNN, SchNet
+    if not isinstance(model, (CGCNN, SchNet, MEGNet, MPNN)):
+        raise ops.MdlError("energy_and_forces: forces are implemented for CGCNN and SchNet, MEGNet and MPNN (got %s); GCN's edge "
+                           "weight is the raw distance inside a degree normalisation, which has no distance gradient here "
+                           "(DESIGN.md)" % type(model).__name__)
     schnet = isinstance(model, SchNet)
     dev = next(model.parameters()).device
     if dev.type != "cuda":
-        raise ops.MdlError("energy_and_forces: the model must be a CGCNN or SchNet on a HIP device (got %s)" % dev)
+        raise ops.MdlError("energy_and_forces: the model must be a CGCNN, SchNet, MEGNet or MPNN on a HIP device (got %s)" % dev)
     lo, hi = float(dist_range[0]), float(dist_range[1])
     if not hi > lo:
         raise ops.MdlError("energy_and_forces: dist_range must be (min, max) with max > min")
@@ -104,7 +112,14 @@ def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, 
         d_norm = (dist - lo) / (hi - lo)                       # fp32, the arithmetic of GraphDataset.dist_norm
         if "expansion" not in routes:
             d_norm = d_norm.detach()
-        G = model.conv_list[0].mlp[0].in_features if schnet else model.conv_list[0].dim
+        if schnet:
+            G = model.conv_list[0].mlp[0].in_features
+        elif isinstance(model, MEGNet):
+            G = model.e_embed_list[0][0].in_features
+        elif isinstance(model, MPNN):
+            G = model.conv_list[0].nn[0].in_features
+        else:
+            G = model.conv_list[0].dim
         cd = model.compute_dtype
         offsets = ops.rbf_offsets(0.0, 1.0, G, dev)
         # SchNet's energy depends on the distance through the expansion AND through the cosine cutoff of the raw distance
@@ -120,5 +135,7 @@ def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, 
             energy = pred[:, int(output_index)].sum()
         else:
             energy = pred.sum()
-        (gpos,) = torch.autograd.grad(energy, pos_g)
+        (gpos,) = torch.autograd.grad(energy, pos_g, allow_unused=True)
+        if gpos is None:                                       # no route carries the derivative (routes without "expansion")
+            gpos = torch.zeros_like(pos_g)
     return pred.detach(), (-gpos).float(), node_ptr

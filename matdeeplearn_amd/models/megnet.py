@@ -109,10 +109,11 @@ def _embed(i, d):
     return nn.Sequential(nn.Linear(i, d), nn.ReLU(), nn.Linear(d, d), nn.ReLU())
 
 
-def _run_embed(seq, h):
+def _run_embed(seq, h, dist=None):
     """Sequential(Linear, ReLU, Linear, ReLU) (megnet.py:222-247) with each Linear + ReLU pair as one fused dense layer and
-    the first ReLU's derivative handed to the second layer's backward (nn._seq)."""
-    return _seq(seq, h)
+    the first ReLU's derivative handed to the second layer's backward (nn._seq).  dist: h is the Gaussian expansion of
+    dist[0]; a gradient asked of it comes from the first layer's distance epilogue (ops.rbf_linear_act)."""
+    return _seq(seq, h, dist=dist)
 
 
 class _FusedMetaLayer(MetaLayer):
@@ -181,8 +182,11 @@ class MEGNet(GraphModel):
         elif cd == torch.bfloat16:                   # int32 gather indices of the fused edge block, once per batch
             idx = (ei[0].to(torch.int32), ei[1].to(torch.int32), data.batch)
         x = e = u = None
+        # (d_norm, offsets, coeff) when edge_attr is the expansion of d_norm: the only place the model reads it is the first
+        # layer of e_embed_list[0], whose backward then returns dL/dd_norm (the force path of matdeeplearn_amd.forces)
+        dist = getattr(data, "dist", None)
         for i, conv in enumerate(self.conv_list):
-            e_t = _run_embed(self.e_embed_list[i], data.edge_attr.to(cd) if i == 0 else e)
+            e_t = _run_embed(self.e_embed_list[i], data.edge_attr.to(cd) if i == 0 else e, dist if i == 0 else None)
             x_t = _run_embed(self.x_embed_list[i], out if i == 0 else x)
             u_t = _run_embed(self.u_embed_list[i], data.u.to(cd) if i == 0 else u)
             # (the edge residual is formed inside the layer, together with the by-source mean of its edge output)

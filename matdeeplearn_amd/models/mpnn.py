@@ -57,8 +57,9 @@ class MPNN(GraphModel):
         cd = self.compute_dtype
         out = self._pre(x)                  # NNConv (K7) + BatchNorm in the compute dtype; the GRU state in fp32
         h = out.float()
+        dist = getattr(data, "dist", None)   # (d_norm, offsets, coeff): edge_attr is its expansion (forces: every layer returns dL/dd_norm)
         for i, conv in enumerate(self.conv_list):
-            m = self._bn(i, conv(out, None, edge_attr, csr=csr))
+            m = self._bn(i, conv(out, None, edge_attr, csr=csr, dist=dist))
             m = self._drop(getattr(F, self.act)(m))
             gru = self.gru_list[i]
             if gru.num_layers == 1 and not gru.bidirectional and gru.bias:

@@ -108,13 +108,16 @@ def _lin(lin, h, act=None, in_act=None, out_pre=False, pre=None):
     return ops.linear_act(h, lin.weight, lin.bias, act, lowp_copies(lin), in_act, out_pre, pre)
 
 
-def _seq(seq, h, pre=None):
+def _seq(seq, h, pre=None, dist=None):
     """Sequential of Linear / activation modules; a Linear followed by ShiftedSoftplus / ReLU runs as ONE fused dense layer.
     Between two fused layers of the chain the intermediate tensor is private to this function, so the activation derivative
     is handed down the chain (ops._LinearActTN: the later layer's backward returns the gradient w.r.t. the earlier layer's
     pre-activation, the earlier layer's backward reads neither its output nor applies a derivative).
     pre: the outputs of the chain's Linear layers, already formed by a fused forward (CFConv: ops.cfconv_fused) — every layer
-    must then take the fused dense path, whose autograd node only records the graph."""
+    must then take the fused dense path, whose autograd node only records the graph.
+    dist = (d_norm [E] fp32, offsets [G], coeff): h is rbf_expand(d_norm), detached.  When d_norm requires a gradient the first
+    layer goes through ops.rbf_linear_act (csrc/linear_de.hip returns dL/dd_norm; same forward, same weight gradients); with
+    none asked the routing is what it always was."""
     mods = list(seq)
     layers, k = [], 0                                   # (module, act) per step; act is None for non-Linear modules
     while k < len(mods):
@@ -129,6 +132,9 @@ def _seq(seq, h, pre=None):
             k += 1
     handed = False                                      # the previous step was a fused layer told to expect a pre-activation gradient
     pre = list(pre) if pre is not None else None
+    want_dd = dist is not None and torch.is_grad_enabled() and dist[0].requires_grad
+    if want_dd and not (layers and layers[0][1] is not False):
+        h, want_dd = ops.expansion_of(dist, h.dtype), False            # no dense layer in front: the expansion carries the gradient
     for j, (m, act) in enumerate(layers):
         if act is False:
             assert pre is None
@@ -142,7 +148,10 @@ def _seq(seq, h, pre=None):
                 and ops._hip_shape_ok(nxt[0].out_features, nxt[0].in_features)
                 and (nxt[1] != "ssp" or nxt[0].out_features % 2 == 0) and h.shape[0] >= ops._DENSE_MIN_ROWS)
         prev_act = layers[j - 1][1] if handed else None
-        if fused:
+        if want_dd and j == 0:
+            assert pre is None
+            h = ops.rbf_linear_act(h, m.weight, m.bias, act, dist, lowp_copies(m), out_pre=fused and give, layer=m)
+        elif fused:
             h = _lin(m, h, act, in_act=prev_act, out_pre=give, pre=pre.pop(0) if pre else None)
         else:
             assert not handed and pre is None
@@ -323,14 +332,17 @@ class NNConv(nn.Module):
             return last
         return None
 
-    def forward(self, x, edge_index, edge_attr, csr=None):
+    def forward(self, x, edge_index, edge_attr, csr=None, dist=None):
+        """dist = (d_norm [E] fp32, offsets [G], coeff): edge_attr = rbf_expand(d_norm), detached.  A gradient asked of d_norm is
+        served by the first layer of the edge network (ops.rbf_linear_act, csrc/linear_de.hip) on the re-associated path, by the
+        general composition (the expansion carries it) on the chunked fallback; with none asked nothing changes."""
         from torch.utils.checkpoint import checkpoint
         if csr is None:
             csr = ops.csr_for(edge_index, x.shape[0])
         last = self._last_linear()
         ci, co = self.in_channels, self.out_channels
         if last is not None and (co * (last.in_features + 1) + last.in_features + co) * 4 <= 160 * 1024:
-            hdn = _seq(list(self.nn)[:-1], edge_attr)
+            hdn = _seq(list(self.nn)[:-1], edge_attr, dist=dist)
             d3 = last.in_features
             w2 = last.weight.view(ci, co * d3).to(x.dtype)
             Y = ops.matmul_wide(x, w2)                                    # [N, C_out*d3]: the only large dense product
@@ -350,6 +362,8 @@ class NNConv(nn.Module):
             if self.bias is not None:
                 out = out + self.bias.to(out.dtype)
             return out
+        if dist is not None and torch.is_grad_enabled() and dist[0].requires_grad:
+            edge_attr = ops.expansion_of(dist, edge_attr.dtype)
         xj = ops.gather(x, csr.row)                                   # caller's edge order
         parts = []
         for s in range(0, csr.E, self.chunk):

@@ -1980,6 +1980,131 @@ def linear_act(x, weight, bias, act, lowp=None, in_act=None, out_pre=False, pre=
     return getattr(torch.nn.functional, act)(y)
 
 
+# ------------------------------------------------------------------------------------------------
+# First-edge-layer distance gradient (csrc/linear_de.hip): forces for MEGNet and MPNN.  In both models the positions enter
+# through a Linear(G -> M) + ReLU applied to edge_attr = rbf_expand(d_norm); the layer's input gradient collapses through the
+# expansion to one number per edge inside the kernel, and no [E, G] gradient is stored.
+# ------------------------------------------------------------------------------------------------
+# launches of mdl_linear_rbf_dist_grad (tests assert that the kernel, not the general composition, served a case)
+LIN_DD_LAUNCHES = collections.Counter()
+
+
+def linear_dist_ok(y, weight):
+    """mdl_linear_rbf_dist_grad takes the gradient of this layer output: [E, M] fp32 / bf16 rows on a HIP device, M <= 256, G <= 64"""
+    if not (y.is_cuda and y.dim() == 2 and weight.dim() == 2 and y.shape[1] == weight.shape[0]
+            and y.dtype in (torch.float32, torch.bfloat16)):
+        return False
+    return bool(lib().mdl_linear_rbf_dist_grad_supported(weight.shape[0], weight.shape[1], dtype_code(y)))
+
+
+def _rows(t):
+    """t [E, M] with unit column stride and a leading dimension >= M (what autograd hands a backward may be an expanded view)"""
+    return t if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) else t.contiguous()
+
+
+def _linear_dd_launch(g, act_y, w, d_norm, offsets, coeff, scale, dd, accumulate):
+    """mdl_linear_rbf_dist_grad: dd [E] fp32 = or += the distance gradient of the layer with weight w [M, G] (g's dtype)"""
+    LIN_DD_LAUNCHES["distance"] += 1
+    E, M = g.shape
+    g = _rows(g)
+    act_y = None if act_y is None else _rows(act_y)
+    check(_launch_timed("linear_dd", lambda: lib().mdl_linear_rbf_dist_grad(
+        ptr(g), g.stride(0) if E > 1 else M, ptr(act_y), M if act_y is None or E <= 1 else act_y.stride(0), ptr(w), dtype_code(g),
+        ptr(d_norm), ptr(offsets), float(coeff), float(scale), ptr(dd), int(bool(accumulate)), E, M, w.shape[1], stream())),
+        "mdl_linear_rbf_dist_grad")
+
+
+class _LinearDist(torch.autograd.Function):
+    """The node BEHIND a dense layer y = act(W rbf_expand(d_norm) + b) that closes the chain to the distance.  Forward: y itself,
+    handed through (the layer's own node made it, bit for bit as ever, and keeps forming dW / db).  Backward: the arriving
+    gradient goes on to the layer's node unchanged, and d_norm receives dL/dd_norm from mdl_linear_rbf_dist_grad.
+    masked: g is the gradient w.r.t. the ReLU output y (the mask is applied in the kernel); otherwise w.r.t. the
+    pre-activation — the chain behind the layer applied the derivative (nn._seq's hand-over) or there is no activation."""
+
+    @staticmethod
+    def forward(ctx, y, w, d_norm, offsets, coeff, masked):
+        ctx.save_for_backward(y if masked else None, w, d_norm, offsets)
+        ctx.coeff = coeff
+        return y.view_as(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        y, w, d_norm, offsets = ctx.saved_tensors
+        dd = None
+        if ctx.needs_input_grad[2]:
+            dd = torch.empty(d_norm.numel(), dtype=torch.float32, device=g.device)
+            _linear_dd_launch(g, y, w, d_norm, offsets, ctx.coeff, 1.0, dd, False)
+        return g, None, dd, None, None, None
+
+
+def expansion_of(dist, dtype):
+    """rbf_expand of dist = (d_norm, offsets, coeff) as a tensor that carries the gradient to d_norm: the general composition"""
+    return _RbfExpand.apply(dist[0].contiguous(), dist[1].float().contiguous(), float(dist[2]), dtype)
+
+
+def rbf_linear_act(edge_attr, weight, bias, act, dist, lowp=None, out_pre=False, fused=True, layer=None):
+    """act(F.linear(edge_attr, weight, bias)) for edge_attr = rbf_expand(d_norm), differentiable in d_norm.
+    dist = (d_norm [E] fp32, offsets [G] fp32, coeff): a promise that edge_attr is the Gaussian expansion of d_norm on these
+    centres (as ops.cgconv / ops.cfconv take it).  The forward is bit for bit the layer's usual one from the given edge_attr —
+    the library product + activation for equal dtypes (`layer`: the module to call for it, e.g. a SplitLinear), ops.linear_act
+    with `lowp` / `out_pre` for bf16 rows (nn._seq's hand-over included) — and the weight and bias gradients come from the same
+    nodes as ever.  When d_norm requires a gradient, one more node behind the layer returns dL/dd_norm from
+    csrc/linear_de.hip; edge_attr is detached and no [E, G] gradient exists.  Other activations than relu / None, shapes the
+    kernel does not take (M > 256, G > 64) and fused=False use the general composition: the expansion carries the gradient,
+    then the dense layer's input gradient and mdl_rbf_expand_bwd."""
+    d_norm, offsets, coeff = _check_dist("rbf_linear_act", dist, edge_attr, "edge_attr")
+    want = torch.is_grad_enabled() and d_norm.requires_grad
+    ok = want and fused and act in ("relu", None) and edge_attr.dim() == 2 and tuple(weight.shape[1:]) == (edge_attr.shape[1],)
+    ok = ok and bool(lib().mdl_linear_rbf_dist_grad_supported(weight.shape[0], weight.shape[1], dtype_code(edge_attr)))
+    if ok:
+        edge_attr = edge_attr.detach()
+    elif want:
+        edge_attr = expansion_of(dist, edge_attr.dtype)
+    if edge_attr.dtype == weight.dtype:
+        y = layer(edge_attr) if layer is not None else torch.nn.functional.linear(edge_attr, weight, bias)
+        if act == "ssp":
+            y = torch.nn.functional.softplus(y) - _LN2
+        elif act is not None:
+            y = getattr(torch.nn.functional, act)(y)
+    else:
+        y = linear_act(edge_attr, weight, bias, act, lowp, None, out_pre, None)
+    if not ok:
+        return y
+    if lowp is not None and lowp[0].dtype == y.dtype:
+        w = lowp[0].detach()
+    else:
+        w = weight.detach().to(y.dtype)
+    return _LinearDist.apply(y, w.contiguous(), d_norm, offsets.float().contiguous(), float(coeff), act == "relu" and not out_pre)
+
+
+def linear_dist_grad(g, weight, d_norm, act_y=None, start=0.0, stop=1.0, resolution=50, width=0.2, scale=1.0, out=None):
+    """dL/dd of ONE dense layer y = act(W rbf_expand(d_norm, start, stop, resolution, width) + b) for the gradient g [E, M]:
+    w.r.t. the layer's pre-activation (act_y None), or w.r.t. its ReLU output act_y [E, M] (the mask is applied in the kernel).
+    weight [M, resolution] is used in g's dtype (fp32, or the bf16 copy the forward multiplies); g and act_y may be column
+    slices of wider tensors.  `scale` is the chain-rule factor of the caller's normalisation.  Returns [E] fp32; `out` ([E]
+    fp32) is added into instead, so that the layers of a model accumulate in one buffer.  Purely per edge: any edge order, no
+    atomics, bitwise repeatable.  No gradient flows through this call itself."""
+    require_hip(g, weight, d_norm)
+    with torch.no_grad():
+        G = int(resolution)
+        if g.dim() != 2 or tuple(weight.shape) != (g.shape[1], G) or not linear_dist_ok(g, weight):
+            raise MdlError("linear_dist_grad: unsupported g %s / weight %s %s (mdl_linear_rbf_dist_grad_supported)"
+                           % (tuple(g.shape), tuple(weight.shape), g.dtype))
+        E = g.shape[0]
+        if d_norm.dtype != torch.float32 or d_norm.numel() != E:
+            raise MdlError("linear_dist_grad: d_norm must be [E] float32 over the %d rows of g" % E)
+        if act_y is not None and (act_y.shape != g.shape or act_y.dtype != g.dtype):
+            raise MdlError("linear_dist_grad: act_y must have g's shape and dtype")
+        if out is not None and (out.dtype != torch.float32 or out.numel() != E or not out.is_contiguous()):
+            raise MdlError("linear_dist_grad: out must be a contiguous [E] float32 tensor")
+        offsets = rbf_offsets(start, stop, G, g.device)
+        dd = out if out is not None else torch.empty(E, dtype=torch.float32, device=g.device)
+        _linear_dd_launch(g.detach(), None if act_y is None else act_y.detach(), weight.detach().to(g.dtype).contiguous(),
+                          d_norm.detach().contiguous(), offsets, rbf_coeff(start, stop, width), scale, dd, out is not None)
+        return dd
+
+
 class _LinearSplitTN(torch.autograd.Function):
     """F.linear on fp32 tensors whose WEIGHT GRADIENT dW = g^T x (contraction over the rows: N ~ 2e5 for a node-level layer) runs
     as three bf16 TN-GEMM launches on (hi, lo)-split operands (mdl_split_bf16 + mdl_gemm_tn, fp32 accumulation) instead of the

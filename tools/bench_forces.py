@@ -1,17 +1,23 @@
 #!/usr/bin/env python3
 """Forces from positions: forces.energy_and_forces on a batch of bulk-like structures, fused distance path vs the general [E, G] path.
 
-  python tools/bench_forces.py [--model cgcnn|schnet] [--graphs 8192] [--dim 64] [--dtypes fp32,bf16] [--repeats 5] [--seed 0]
+  python tools/bench_forces.py [--model cgcnn|schnet|megnet|mpnn] [--graphs 8192] [--dim 64] [--dtypes fp32,bf16] [--repeats 5] [--seed 0]
+  python tools/bench_forces.py --kernel [--edges 2600000] [--widths 64,100] [--dtypes fp32,bf16] [--repeats 20]
 
 Structures are drawn with the size recipe of process.synthetic_bulk (n ~ lognormal(ln 20, 0.7) clipped to [1, 200], cubic periodic
 cell at density 0.05, uniform positions, Z ~ U[1, 89]); the model is a seeded CGCNN (dim1 = dim2 = --dim, 4 conv layers) or, with
---model schnet, a seeded SchNet (dim1 = dim2 = dim3 = --dim, 3 interaction blocks) in eval mode.  The fused and the general
-runs alternate, so both see the same machine state.
+--model schnet, a seeded SchNet (dim1 = dim2 = dim3 = --dim, 3 interaction blocks), with --model megnet / mpnn a seeded MEGNet /
+MPNN (dim1 = dim2 = dim3 = --dim, 3 layers) in eval mode.  The fused and the general runs alternate, so both see the same
+machine state.
 Reported per dtype, one JSON line:
   fused_ms / general_ms   one energy_and_forces call end to end (packing on the host included), device events, best of repeats
   max_abs_diff_rel        max |F_fused - F_general| / max |F|
 The per-layer kernel times (cgconv_de_kernel / cfconv_de_*_kernel in both epilogues, rbf_bwd_kernel, edge_geom_*) come from a kernel trace of this
-script, e.g.  rocprofv3 --kernel-trace --stats -- python tools/bench_forces.py --repeats 2  (a process of its own)."""
+script, e.g.  rocprofv3 --kernel-trace --stats -- python tools/bench_forces.py --repeats 2  (a process of its own).
+--kernel: the first-edge-layer distance gradient alone (csrc/linear_de.hip, masked form: g and the layer's ReLU output are read)
+against the pair it replaces — the layer's input gradient dx = (g * mask) W into [E, G], then mdl_rbf_expand_bwd — on random
+operands, alternating, one JSON line per (dtype, width): fused_us / pair_us (best of repeats, device events) and the achieved
+bytes/s on the kernel's compulsory traffic E (2 M s + 8)."""
 import argparse
 import json
 import os
@@ -59,21 +65,64 @@ def timed(fns, repeats):
     return best, out
 
 
+def kernel_bench(a):
+    from matdeeplearn_amd import _lib, ops
+    dev = torch.device("cuda")
+    E, G = a.edges, 50
+    offs, coeff = ops.rbf_offsets(0.0, 1.0, G, dev), ops.rbf_coeff(0.0, 1.0, 0.2)
+    for dt in a.dtypes.split(","):
+        dtype = {"fp32": torch.float32, "bf16": torch.bfloat16}[dt]
+        for M in [int(v) for v in a.widths.split(",")]:
+            gen = torch.Generator(device=dev).manual_seed(a.seed)
+            g = torch.randn(E, M, device=dev, generator=gen).to(dtype)
+            y = torch.relu(torch.randn(E, M, device=dev, generator=gen)).to(dtype)
+            w = (torch.randn(M, G, device=dev, generator=gen) * 0.3).to(dtype)
+            d = torch.rand(E, device=dev, generator=gen)
+            dd = torch.empty(E, device=dev)
+
+            def pair():
+                if ops._dx_hip_ok(g, w):
+                    dx = ops._dx_hip(g, w, (1, y))                      # the mask in the streaming kernel's staging
+                else:
+                    dx = torch.ops.aten.threshold_backward(g, y, 0) @ w
+                _lib.check(_lib.lib().mdl_rbf_expand_bwd(_lib.ptr(dx), G, _lib.dtype_code(dx), _lib.ptr(d), _lib.ptr(offs), coeff,
+                                                         _lib.ptr(dd), E, G, _lib.stream()), "mdl_rbf_expand_bwd")
+                return dd.clone()
+
+            fused = lambda: ops.linear_dist_grad(g, w, d, act_y=y, resolution=G)
+            fused(), pair()
+            (t_f, t_p), (r_f, r_p) = timed([fused, pair], a.repeats)
+            nbytes = E * (2 * M * g.element_size() + 8)
+            print(json.dumps({"kernel": "linear_rbf_dist_grad", "dtype": dt, "edges": E, "M": M, "G": G, "fused_us": round(t_f * 1e3, 1),
+                              "pair_us": round(t_p * 1e3, 1), "fused_TBps": round(nbytes / (t_f * 1e-3) / 1e12, 3),
+                              "max_abs_diff_rel": float((r_f - r_p).abs().max() / r_f.abs().max())}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=("cgcnn", "schnet"), default="cgcnn")
+    ap.add_argument("--model", choices=("cgcnn", "schnet", "megnet", "mpnn"), default="cgcnn")
+    ap.add_argument("--kernel", action="store_true", help="time csrc/linear_de.hip alone against dx + mdl_rbf_expand_bwd")
+    ap.add_argument("--edges", type=int, default=2600000)
+    ap.add_argument("--widths", default="64,100")
     ap.add_argument("--graphs", type=int, default=8192)
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--dtypes", default="fp32,bf16")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
+    if a.kernel:
+        if a.repeats == 5:
+            a.repeats = 20
+        return kernel_bench(a)
     dev = torch.device("cuda")
     packed = pg.pack_structures(structures(a.graphs, a.seed))
     for dt in a.dtypes.split(","):
         torch.manual_seed(a.seed)
         if a.model == "schnet":
             model = models.SchNet(DS(), dim1=a.dim, dim2=a.dim, dim3=a.dim, gc_count=3, post_fc_count=1, compute_dtype=dt).to(dev).eval()
+        elif a.model in ("megnet", "mpnn"):
+            cls = models.MEGNet if a.model == "megnet" else models.MPNN
+            model = cls(DS(), dim1=a.dim, dim2=a.dim, dim3=a.dim, gc_count=3, post_fc_count=1, compute_dtype=dt).to(dev).eval()
         else:
             model = models.CGCNN(DS(), dim1=a.dim, dim2=a.dim, gc_count=4, post_fc_count=1, compute_dtype=dt).to(dev).eval()
         run = lambda fused: forces.energy_and_forces(model, packed, (0.0, 8.0), fused=fused)
