@@ -644,6 +644,20 @@ int mdl_edge_geometry_bwd(const float* dd, const float* u, const int32_t* rowptr
                           const int32_t* rowptr_s, const int32_t* eid_s, int64_t N, int64_t E, float* dpos,
                           mdlStream_t stream);
 
+/* Strain gradient of the energy per graph (stress times volume): out [G, 3, 3] fp32 (every row written, symmetric to the bit)
+ *   out[g] = sum over the edges e of graph g of  dd[e] dist[e] u[e] (x) u[e]
+ * = dE/d eps at eps = 0 for a homogeneous strain v -> (I + eps) v of every edge displacement, at fixed neighbour lists and images.
+ * dd / dist [E], u [E, 3] fp32 (dd = dE/d dist; dist and u as mdl_edge_geometry_fwd wrote them); rowptr_t [N + 1] / eid_t: CSR by
+ * target as for mdl_edge_geometry_bwd (eid NULL = the slot is the edge id; ids outside [0, E) are skipped); node_ptr [G + 1] int64.
+ * The edges of graph g are the slots [rowptr_t[node_ptr[g]], rowptr_t[node_ptr[g + 1]]).  One workgroup per (graph, slice) with
+ * `slices` slices per graph (0: chosen from E and G alone); more than one slice needs the workspace of
+ * mdl_edge_strain_grad_workspace_bytes(G, E, slices) bytes (8-byte aligned) for fp64 partial sums, added in slice order by a
+ * second launch.  fp64 accumulation, no atomics: bitwise repeatable.  Graphs without atoms or edges, and E = 0, give zeros. */
+size_t mdl_edge_strain_grad_workspace_bytes(int64_t G, int64_t E, int32_t slices);
+int mdl_edge_strain_grad(const float* dd, const float* dist, const float* u, const int32_t* rowptr_t, const int32_t* eid_t,
+                         const int64_t* node_ptr, int64_t N, int64_t G, int64_t E, int32_t slices, float* out, void* workspace,
+                         size_t workspace_bytes, mdlStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,8 @@ PROTOTYPES = {
     "mdl_edge_geometry_workspace_bytes": (_sz, [_i64]),
     "mdl_edge_geometry_fwd": (_i32, [_vp] * 4 + [_i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "mdl_edge_geometry_bwd": (_i32, [_vp] * 6 + [_i64, _i64, _vp, _vp]),
+    "mdl_edge_strain_grad_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "mdl_edge_strain_grad": (_i32, [_vp] * 6 + [_i64, _i64, _i64, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

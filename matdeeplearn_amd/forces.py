@@ -17,7 +17,11 @@ Chain, one public call (energy_and_forces):
                         (once per layer).  ops.rbf_linear_act puts a node behind that layer whose backward returns dL/dd from
                         csrc/linear_de.hip; everything behind it (gathers, scatters, BatchNorm, nnconv_msg, the GRU gates) is
                         differentiable in its inputs as it is
-No gradient w.r.t. the cell (stress) and no second derivatives (training on forces): both raise or are absent by construction."""
+The derivative w.r.t. the cell (energy_forces_stress): at fixed neighbour lists and images a homogeneous strain eps maps every
+edge displacement v to (I + eps) v, and d|v|/d eps_ab = v_a v_b / |v|, so dE/d eps_ab of structure b = sum over its edges of
+(dE/dd_e) d_e u_e,a u_e,b — one reduction (ops.edge_strain_grad, csrc/edge_geom.hip) over the gradient w.r.t. the distances that
+the same backward already forms, not a second derivative chain.
+No second derivatives (training on forces): every backward is once_differentiable."""
 import numpy as np
 import torch
 
@@ -75,8 +79,39 @@ def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, 
 
     Returns (pred [B] or [B, out] fp32, forces [N, 3] fp32, node_ptr [B + 1] int64), device tensors; atom n of structure b is row
     node_ptr[b] + n.  The neighbour lists are built once from the given positions and HELD FIXED under the derivative; the image
-    shifts and the cell are constants too (no stress).  Forces of a graph sum to zero up to fp32 rounding; with
-    ops.deterministic() two calls return the same bits."""
+    shifts and the cell are constants too (the strain derivative: energy_forces_stress).  Forces of a graph sum to zero up to
+    fp32 rounding; with ops.deterministic() two calls return the same bits."""
+    pred, gpos, _, node_ptr, _ = _energy_gradients(model, structs, dist_range, radius, max_neighbors, dictionary, output_index, fused, routes,
+                                                   False)
+    return pred, (-gpos).float(), node_ptr
+
+
+def energy_forces_stress(model, structs, dist_range, radius=8.0, max_neighbors=12, dictionary=None, output_index=None, fused=True,
+                         routes=("expansion", "cutoff"), volume_normalised=True):
+    """Prediction, forces and stress of a CGCNN, SchNet, MEGNet or MPNN: energy_and_forces (same arguments, same pred and forces)
+    plus the derivative w.r.t. a homogeneous strain of each structure.
+
+    Returns (pred, forces [N, 3] fp32, stress [B, 3, 3] fp32, node_ptr).  stress[b] = (1 / V_b) dE/d eps, tensile positive, with
+    dE/d eps_ab = sum over the edges of b of (dE/dd_e) d_e u_e,a u_e,b at fixed neighbour lists and images (positions, cell and
+    shifts deform together) and V_b = |a . (b x c)| of the fp64 cell.  A structure that is not periodic in all three directions,
+    or whose cell has no volume, has no stress: its row is NaN.  volume_normalised=False returns dE/d eps itself (an energy) for
+    every structure.  Symmetric to the bit; the gradient w.r.t. the distances is taken in the backward that gives the forces and
+    covers both of SchNet's routes."""
+    pred, gpos, strain, node_ptr, (cell, pbc) = _energy_gradients(model, structs, dist_range, radius, max_neighbors, dictionary, output_index,
+                                                                  fused, routes, True)
+    if volume_normalised:
+        a, b, c = cell[:, 0], cell[:, 1], cell[:, 2]
+        vol = (a[:, 0] * (b[:, 1] * c[:, 2] - b[:, 2] * c[:, 1]) + a[:, 1] * (b[:, 2] * c[:, 0] - b[:, 0] * c[:, 2])
+               + a[:, 2] * (b[:, 0] * c[:, 1] - b[:, 1] * c[:, 0])).abs()
+        periodic = (pbc != 0).all(1) if pbc.dim() == 2 else (pbc & 7) == 7
+        has_volume = periodic & (vol > 0)
+        inv = torch.where(has_volume, 1.0 / torch.where(has_volume, vol, torch.ones_like(vol)), torch.full_like(vol, float("nan")))
+        strain = (strain.double() * inv.view(-1, 1, 1)).float()
+    return pred, (-gpos).float(), strain, node_ptr
+
+
+def _energy_gradients(model, structs, dist_range, radius, max_neighbors, dictionary, output_index, fused, routes, want_strain):
+    """The body of energy_and_forces / energy_forces_stress: (pred, dE/dpos, dE/d eps [B, 3, 3] or None, node_ptr, (cell, pbc))"""
     from .models import CGCNN, MEGNet, MPNN, SchNet
     if not isinstance(model, (CGCNN, SchNet, MEGNet, MPNN)):
         raise ops.MdlError("energy_and_forces: forces are implemented for CGCNN and SchNet, MEGNet and MPNN (got %s); GCN's edge "
@@ -108,7 +143,10 @@ def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, 
 
     with torch.enable_grad():
         pos_g = pos.detach().requires_grad_(True)
-        dist = ops.edge_vectors(pos_g, node_ptr, cell, pbc, src, tgt, csr=csr)
+        if want_strain:
+            dist, unit = ops.edge_vectors(pos_g, node_ptr, cell, pbc, src, tgt, csr=csr, return_unit=True)
+        else:
+            dist = ops.edge_vectors(pos_g, node_ptr, cell, pbc, src, tgt, csr=csr)
         d_norm = (dist - lo) / (hi - lo)                       # fp32, the arithmetic of GraphDataset.dist_norm
         if "expansion" not in routes:
             d_norm = d_norm.detach()
@@ -135,7 +173,15 @@ def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, 
             energy = pred[:, int(output_index)].sum()
         else:
             energy = pred.sum()
-        (gpos,) = torch.autograd.grad(energy, pos_g, allow_unused=True)
+        if want_strain:                                        # dE/dd: the sum of every route's gradient, as the geometry's backward gets it
+            gpos, gdist = torch.autograd.grad(energy, [pos_g, dist], allow_unused=True)
+        else:
+            (gpos,), gdist = torch.autograd.grad(energy, pos_g, allow_unused=True), None
         if gpos is None:                                       # no route carries the derivative (routes without "expansion")
             gpos = torch.zeros_like(pos_g)
-    return pred.detach(), (-gpos).float(), node_ptr
+        strain = None
+        if want_strain:
+            if gdist is None:
+                gdist = torch.zeros_like(dist)
+            strain = ops.edge_strain_grad(gdist, dist.detach(), unit, node_ptr, csr=csr)
+    return pred.detach(), gpos, strain, node_ptr, (cell, pbc)

@@ -2594,7 +2594,8 @@ def edge_vectors(pos, node_ptr, cell, pbc, src, tgt, edge_ptr=None, csr=None, re
     image: reduced cell, completed basis, rint wrap, +-1 images) — and with return_unit=True also u [E, 3] fp32, the unit vector
     of the displacement p_tgt - p_src + shift (0 for self loops and coincident atoms; carries no gradient).
     The backward is dpos[tgt] += g u, dpos[src] -= g u as two segmented sums (by target and by source: no atomics, bitwise
-    repeatable).  The image shifts and the cell are held fixed: there is no gradient w.r.t. `cell` (stress is out of scope).
+    repeatable).  The image shifts and the cell are held fixed: there is no gradient w.r.t. `cell` under autograd; the strain
+    gradient (stress) comes from the gradient w.r.t. `dist` through edge_strain_grad.
     csr: an EdgeCSR of the batch-global edge list, if the caller has one (saves the backward its two sorts)."""
     pos, node_ptr, cell, pbc, G = _graph_args(pos, node_ptr, cell, pbc)
     require_hip(src, tgt)
@@ -2609,3 +2610,45 @@ def edge_vectors(pos, node_ptr, cell, pbc, src, tgt, edge_ptr=None, csr=None, re
         raise MdlError("edge_vectors: csr does not match the edge list")
     dist, u = _EdgeVectors.apply(pos, node_ptr, cell, pbc, src.contiguous(), tgt.contiguous(), csr)
     return (dist, u) if return_unit else dist
+
+
+def edge_strain_grad(g_dist, dist, u, node_ptr, csr=None, src=None, tgt=None, _slices=None):
+    """Strain gradient of the energy per graph from the gradient w.r.t. the edge distances (csrc/edge_geom.hip).
+      g_dist [E] = dE/d dist (what autograd hands to the backward of edge_vectors), dist [E] fp32 and u [E, 3] fp32 as
+      edge_vectors(..., return_unit=True) returned them, node_ptr [G + 1] int64.
+      csr: the EdgeCSR (by target) of the batch-global edge list; without one it is built from src / tgt [E] int32 (one stable
+      sort, and one number read back for the atom count).
+    Returns [G, 3, 3] fp32:  out[g] = sum_{e in g} g_e d_e u_e (x) u_e = dE/d eps of a homogeneous strain v -> (I + eps) v of the
+    structure (positions, cell and image shifts together) at fixed neighbour lists — stress times volume, tensile positive.
+    Symmetric to the bit, fp64 accumulation, no atomics: two calls give the same bits.  Not an autograd node: g_dist is a number."""
+    require_hip(g_dist, dist, u, node_ptr)
+    E = dist.numel()
+    if dist.dtype != torch.float32 or dist.dim() != 1 or u.dtype != torch.float32 or tuple(u.shape) != (E, 3):
+        raise MdlError("edge_strain_grad: dist must be [E] float32 and u [E, 3] float32 (got %s %s, %s %s)"
+                       % (tuple(dist.shape), dist.dtype, tuple(u.shape), u.dtype))
+    if not g_dist.is_floating_point() or tuple(g_dist.shape) != (E,):
+        raise MdlError("edge_strain_grad: g_dist must be [E] floating point with E = %d (got %s %s)" % (E, tuple(g_dist.shape), g_dist.dtype))
+    if node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 2:
+        raise MdlError("edge_strain_grad: node_ptr must be [G + 1] int64 with G >= 1")
+    if any(t.device != dist.device for t in (g_dist, u, node_ptr)):
+        raise MdlError("edge_strain_grad: g_dist, dist, u and node_ptr must be on one device")
+    if csr is None:
+        if src is None or tgt is None:
+            raise MdlError("edge_strain_grad: needs the EdgeCSR of the edge list, or src / tgt to build it")
+        require_hip(src, tgt)
+        if src.dtype != torch.int32 or tgt.dtype != torch.int32 or tuple(src.shape) != (E,) or tuple(tgt.shape) != (E,):
+            raise MdlError("edge_strain_grad: src / tgt must be [E] int32")
+        csr = build_csr(torch.stack([src, tgt]), int(node_ptr[-1]))
+    if csr.E != E or csr.rowptr.device != dist.device:
+        raise MdlError("edge_strain_grad: csr does not match the edge list")
+    S = 0 if _slices is None else int(_slices)
+    if _slices is not None and not 1 <= S <= 65536:
+        raise MdlError("edge_strain_grad: _slices must be in [1, 65536] (got %d)" % S)
+    G = node_ptr.numel() - 1
+    out = torch.empty((G, 3, 3), dtype=torch.float32, device=dist.device)
+    nbytes = lib().mdl_edge_strain_grad_workspace_bytes(G, E, S)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dist.device)
+    check(lib().mdl_edge_strain_grad(ptr(g_dist.detach().float().contiguous()), ptr(dist.detach().contiguous()), ptr(u.contiguous()),
+                                     ptr(csr.rowptr), ptr(csr.eperm), ptr(node_ptr.contiguous()), csr.N, G, E, S, ptr(out), ptr(ws),
+                                     nbytes, stream()), "mdl_edge_strain_grad")
+    return out
