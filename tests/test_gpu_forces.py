@@ -95,12 +95,17 @@ def _de_case(n, C, G, dtype, sort, seed, aggr="mean", empty_frac=0.1, window=40)
     close(bsd.grad, bso.grad, *tol, what="db_s")
 
 
+SPARSE_N, SPARSE_EMPTY = 2000, 0.93      # the sparse graph of tests/test_gpu_kernels.py: 93 % of 2000 nodes without edges
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("n,C,G,sort", [(200, 64, 50, True), (200, 64, 50, False), (77, 32, 50, True),
                                          (130, 100, 50, False), (65, 128, 50, True), (900, 100, 50, True), (50, 64, 41, True),
-                                         (33, 20, 7, False), (1, 64, 50, True)])
+                                         (33, 20, 7, False), (1, 64, 50, True),
+                                         # bias from bpack (G % 16 == 0), element loads of x (C % 4 != 0), N > E with most nodes isolated
+                                         (200, 64, 64, True), (100, 32, 16, True), (100, 30, 7, True), (SPARSE_N, 64, 50, True)])
 def test_cgconv_edge_attr_gradient_matches_oracle(dtype, n, C, G, sort):
-    _de_case(n, C, G, dtype, sort, seed=n + C + G)
+    _de_case(n, C, G, dtype, sort, seed=n + C + G, empty_frac=SPARSE_EMPTY if n == SPARSE_N else 0.1)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -180,7 +185,8 @@ def _dist_case(n, C, G, dtype, sort, seed, aggr="mean"):
 
 
 @pytest.mark.parametrize("n,C,G,sort,aggr", [(200, 64, 50, True, "mean"), (200, 64, 50, False, "mean"), (130, 100, 50, False, "add"),
-                                              (33, 20, 7, False, "mean"), (900, 100, 50, True, "mean"), (50, 64, 41, True, "add")])
+                                              (33, 20, 7, False, "mean"), (900, 100, 50, True, "mean"), (50, 64, 41, True, "add"),
+                                              (200, 64, 64, True, "mean")])        # G % 16 == 0: the bias from bpack under the fused epilogue
 def test_cgconv_distance_epilogue_matches_oracle_fp32(n, C, G, sort, aggr):
     """dL/dd_norm of one layer through rbf_expand + cgconv: bound close(2e-5, 2e-5) — kept where the fp32 CPU oracle agrees with the
     fp64 CPU oracle to 5e-6 of the scale, else 4x that reference-vs-reference error.  Measured on the CPU for these cases: the fp32

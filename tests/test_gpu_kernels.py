@@ -130,12 +130,21 @@ def _cgconv_case(n, C, G, dtype, sort, seed, aggr="mean", empty_frac=0.1, window
     close(bsd.grad, bso.grad, *tol)
 
 
+SPARSE_N, SPARSE_EMPTY = 2000, 0.93      # 2000 nodes, 93 % of them without edges: about 1600 edges in 63 groups of 32 nodes
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("n,C,G,sort", [(200, 64, 50, True), (200, 64, 50, False), (77, 32, 50, True),
                                          (130, 100, 50, False), (65, 128, 50, True), (900, 100, 50, True), (50, 64, 41, True),
-                                         (33, 20, 7, False), (1, 64, 50, True)])
+                                         (33, 20, 7, False), (1, 64, 50, True),
+                                         # G % 16 == 0: the bias comes from bpack, not from a K column (cg_launch: bias_col == 0)
+                                         (200, 64, 64, True), (100, 32, 16, True),
+                                         # C % 4 != 0: element loads of the x rows (vec == 1)
+                                         (100, 30, 7, True),
+                                         # N > E, most nodes isolated: the backward's dynamic group schedule with its half-group tail
+                                         (SPARSE_N, 64, 50, True)])
 def test_cgconv_matches_oracle(dtype, n, C, G, sort):
-    _cgconv_case(n, C, G, dtype, sort, seed=n + C + G)
+    _cgconv_case(n, C, G, dtype, sort, seed=n + C + G, empty_frac=SPARSE_EMPTY if n == SPARSE_N else 0.1)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
