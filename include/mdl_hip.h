@@ -658,6 +658,30 @@ int mdl_edge_strain_grad(const float* dd, const float* dist, const float* u, con
                          const int64_t* node_ptr, int64_t N, int64_t G, int64_t E, int32_t slices, float* out, void* workspace,
                          size_t workspace_bytes, mdlStream_t stream);
 
+/* ---- Set2Set readout (csrc/set2set.hip) — torch_geometric.nn.Set2Set with a one-layer LSTM, the reference's pool = "set2set"
+ * (matdeeplearn/models/cgcnn.py:112-119,152), all processing steps in ONE launch per direction.  For every segment s of rowptr
+ * [S + 1] (rows rowptr[s] .. rowptr[s+1]-1 of x [N, C] in `dtype`, read as stored; all arithmetic fp32), from q*_0 = 0,
+ * h_0 = c_0 = 0, for t = 1..T:
+ *     G_t = W_ih q*_{t-1} + b_ih + W_hh h_{t-1} + b_hh            (4C; torch's gate order i | f | g | o)
+ *     c_t = sigmoid(f) c_{t-1} + sigmoid(i) tanh(g);  q_t = h_t = sigmoid(o) tanh(c_t)
+ *     e_n = <x_n, q_t>;  a_n = exp(e_n - max e) / (sum exp(e_n - max e) + 1e-16);  r_t = sum a_n x_n;  q*_t = [q_t | r_t]
+ * out [S, 2C] fp32 = q*_T.  w_ih [4C, 2C], w_hh [4C, C], b_ih / b_hh [4C]: the fp32 tensors of torch.nn.LSTM(2C, C).
+ * Saved state for the backward, all fp32, all five or all NULL: gates [T, S, 4C] (ACTIVATED i, f, g, o), c / q / r [T, S, C],
+ * a [T, N] (rows outside every segment are not written).  An empty segment gives r_t = 0; the segment length is unbounded
+ * (rows are streamed).  Rows of x outside [rowptr[0], rowptr[S]) are never read.
+ *   bwd: g [S, 2C] fp32 = dL/dout; da_ws: [T, N] fp32 workspace (contents undefined on entry and exit), needed when dx != NULL;
+ *        dx [N, C] in `dtype` or NULL: written once, rows outside every segment as exact zeros;
+ *        dG [T, S, 4C] fp32 = dL/dG_t (pre-activation).  The parameter gradients are dense products of the caller:
+ *        dW_ih = sum_t dG_t^T q*_{t-1}, dW_hh = sum_t dG_t^T h_{t-1}, db_ih = db_hh = sum_{t,s} dG_t.
+ * 1 <= C <= 128, 1 <= T <= 8, MDL_F32 / MDL_BF16 (mdl_set2set_supported), else MDL_E_UNSUPP.  No atomics: bitwise repeatable. */
+int mdl_set2set_supported(int C, int T, int dtype);
+int mdl_set2set_fwd(const void* x, const int32_t* rowptr, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                    float* out, float* gates, float* c, float* q, float* r, float* a, int64_t N, int64_t S, int C, int T, int dtype,
+                    mdlStream_t stream);
+int mdl_set2set_bwd(const void* x, const int32_t* rowptr, const float* w_ih, const float* w_hh, const float* g, const float* gates,
+                    const float* c, const float* q, const float* r, const float* a, float* da_ws, void* dx, float* dG, int64_t N,
+                    int64_t S, int C, int T, int dtype, mdlStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

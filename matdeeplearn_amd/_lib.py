@@ -145,6 +145,9 @@ PROTOTYPES = {
     "mdl_edge_geometry_bwd": (_i32, [_vp] * 6 + [_i64, _i64, _vp, _vp]),
     "mdl_edge_strain_grad_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "mdl_edge_strain_grad": (_i32, [_vp] * 6 + [_i64, _i64, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "mdl_set2set_supported": (_i32, [_i32, _i32, _i32]),
+    "mdl_set2set_fwd": (_i32, [_vp] * 12 + [_i64, _i64, _i32, _i32, _i32, _vp]),
+    "mdl_set2set_bwd": (_i32, [_vp] * 13 + [_i64, _i64, _i32, _i32, _i32, _vp]),
 }
 
 _lib = None

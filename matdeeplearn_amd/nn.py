@@ -407,8 +407,24 @@ class Set2Set(nn.Module):
         self.lstm = nn.LSTM(self.out_channels, in_channels, num_layers)
         self.lstm.reset_parameters()
 
+    def fused_path(self, x=None):
+        """ops.set2set takes this module's readout of x: one LSTM layer in fp32, the dispatch option on, and rows that
+        ops.set2set_fused_ok accepts — without x: the width and step count the kernels have, for fp32 and bf16 rows
+        (training.driver.graph_replay_wanted asks before any batch exists)"""
+        C, T = self.in_channels, self.processing_steps
+        if not (self.num_layers == 1 and ops._SET2SET_FUSED and self.lstm.weight_ih_l0.dtype == torch.float32):
+            return False
+        if x is not None:
+            return x.dim() == 2 and x.is_cuda and ops.set2set_fused_ok(x, T)
+        return all(bool(ops.lib().mdl_set2set_supported(C, T, d)) for d in (ops._lib.MDL_F32, ops._lib.MDL_BF16))
+
     def forward(self, x, batch, size=None):
         b = int(batch.max()) + 1 if size is None else size
+        if self.fused_path(x):
+            # every processing step in one launch per direction (csrc/set2set.hip); the index is the pools'
+            L = self.lstm
+            return ops.set2set(x, ops._seg_index(batch, b, True), L.weight_ih_l0, L.weight_hh_l0, L.bias_ih_l0, L.bias_hh_l0,
+                               self.processing_steps)
         xf = x.float()
         h = (xf.new_zeros((self.num_layers, b, self.in_channels)), xf.new_zeros((self.num_layers, b, self.in_channels)))
         q_star = xf.new_zeros(b, self.out_channels)

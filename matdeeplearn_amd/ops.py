@@ -642,6 +642,7 @@ OPTIONS = {
     "dense_bwd_wide": ("_DENSE_BWD_WIDE", "... also when both widths exceed 128"),
     "mlp_head": ("_MLP_HEAD", "post-FC head as one launch per direction"),
     "linear_wide": ("_LINEAR_WIDE", "NNConv's Y = x W2r on the streaming kernel"),
+    "set2set_fused": ("_SET2SET_FUSED", "Set2Set readout: all processing steps in one launch per direction (off: torch's LSTM + the composed attention)"),
     "tn_scratch": ("_TN_SCRATCH", "weight-gradient blocks of the TN products as plain stores + a reduce launch (off: atomics from every workgroup)"),
 }
 
@@ -2211,6 +2212,96 @@ def gru_gates(gi, gh, h):
     """One GRU step's gates: returns (h_new [N, C] fp32, out [N, C] in gi's dtype — the same tensor as h_new for fp32)."""
     h_new, out = _GRUGates.apply(gi, gh, h)
     return (h_new, out) if gi.dtype != torch.float32 else (h_new, h_new)
+
+
+# ------------------------------------------------------------------------------------------------
+# Set2Set readout: every processing step in one launch per direction (csrc/set2set.hip)
+# ------------------------------------------------------------------------------------------------
+_SET2SET_FUSED = True
+
+
+class _Set2Set(torch.autograd.Function):
+    """q*_T [S, 2C] fp32 of Set2Set with a one-layer LSTM (cgcnn.py:112-119 via torch_geometric.nn.Set2Set) from x [N, C] and the
+    segment index of its sorted node -> graph map.  Forward: mdl_set2set_fwd (all steps; with the activated gates, c, q, r and the
+    attention weights kept when a gradient is wanted).  Backward: mdl_set2set_bwd (dx, written once, zeros outside the segments,
+    and dG [T, S, 4C]) and the parameter gradients as dense products over the stacked rows: dW_ih = dG[1:]^T [q | r][:-1],
+    dW_hh = dG[1:]^T q[:-1] (h = q: the left half of dW_ih), db_ih = db_hh = column sums of dG (fp32 operands: the library's
+    GEMM — the TN kernel of this package takes bf16 operands only)."""
+
+    @staticmethod
+    def forward(ctx, x, si, w_ih, w_hh, b_ih, b_hh, steps):
+        N, C = x.shape
+        S, T = si.N, int(steps)
+        x = x.contiguous()
+        w_ih, w_hh, b_ih, b_hh = w_ih.contiguous(), w_hh.contiguous(), b_ih.contiguous(), b_hh.contiguous()
+        dev = x.device
+        out = torch.empty((S, 2 * C), dtype=torch.float32, device=dev)
+        gates = cqr = a = None
+        if any(ctx.needs_input_grad):
+            gates = torch.empty((T, S, 4 * C), dtype=torch.float32, device=dev)
+            cqr = torch.empty((3, T, S, C), dtype=torch.float32, device=dev)
+            a = torch.empty((T, N), dtype=torch.float32, device=dev)
+        c, q, r = (cqr[0], cqr[1], cqr[2]) if cqr is not None else (None, None, None)
+        check(lib().mdl_set2set_fwd(ptr(x), ptr(si.rowptr), ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(out), ptr(gates), ptr(c),
+                                    ptr(q), ptr(r), ptr(a), N, S, C, T, dtype_code(x), stream()), "mdl_set2set_fwd")
+        ctx.si, ctx.T = si, T
+        if gates is not None:
+            ctx.save_for_backward(x, w_ih, w_hh, gates, cqr, a)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, w_ih, w_hh, gates, cqr, a = ctx.saved_tensors
+        si, T = ctx.si, ctx.T
+        N, C = x.shape
+        S = si.N
+        need = ctx.needs_input_grad
+        g = g.contiguous().float()
+        dx = torch.empty_like(x) if need[0] else None
+        da = torch.empty((T, N), dtype=torch.float32, device=x.device) if need[0] else None
+        dG = torch.empty((T, S, 4 * C), dtype=torch.float32, device=x.device)
+        check(lib().mdl_set2set_bwd(ptr(x), ptr(si.rowptr), ptr(w_ih), ptr(w_hh), ptr(g), ptr(gates), ptr(cqr[0]), ptr(cqr[1]),
+                                    ptr(cqr[2]), ptr(a), ptr(da), ptr(dx), ptr(dG), N, S, C, T, dtype_code(x), stream()), "mdl_set2set_bwd")
+        dw_ih = dw_hh = db_ih = db_hh = None
+        if need[2] or need[3]:
+            if T > 1 and S > 0:               # (the t = 1 terms vanish: q*_0 = h_0 = 0)
+                qr = torch.cat([cqr[1, :T - 1], cqr[2, :T - 1]], dim=-1).view((T - 1) * S, 2 * C)
+                dw_ih = dG[1:].view((T - 1) * S, 4 * C).t().mm(qr)
+            else:
+                dw_ih = torch.zeros((4 * C, 2 * C), dtype=torch.float32, device=x.device)
+            dw_hh = dw_ih[:, :C].contiguous() if need[3] else None
+            dw_ih = dw_ih if need[2] else None
+        if need[4] or need[5]:
+            db = dG.view(T * S, 4 * C).sum(dim=0)
+            db_ih = db if need[4] else None
+            db_hh = (db.clone() if need[4] else db) if need[5] else None
+        return dx, None, dw_ih, dw_hh, db_ih, db_hh, None
+
+
+def set2set_fused_ok(x, steps):
+    """ops.set2set takes this readout: 2-D fp32 / bf16 rows on a HIP device of a width and step count the kernels have (1 <= C <= 128,
+    1 <= T <= 8 — mdl_set2set_supported)"""
+    return (x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.bfloat16) and x.shape[1] >= 1
+            and bool(lib().mdl_set2set_supported(int(x.shape[1]), int(steps), dtype_code(x))))
+
+
+def set2set(x, seg_index, w_ih, w_hh, b_ih, b_hh, steps):
+    """Set2Set (A.6) of x [N, C] over the segments of `seg_index` — the index `scatter(x, batch, 0, size, ..., assume_sorted=True)`
+    would use (`_seg_index(batch, size, True)`, or make_seg_index) — with the parameters of torch.nn.LSTM(2C, C) (fp32,
+    `weight_ih_l0` [4C, 2C], `weight_hh_l0` [4C, C], the two biases [4C]) and `steps` processing steps: q*_T [S, 2C] fp32.
+    One autograd node, differentiable in x and the four parameters; rows of x outside every segment get a zero gradient."""
+    require_hip(x, w_ih, w_hh, b_ih, b_hh)
+    if not set2set_fused_ok(x, steps):
+        raise MdlError("set2set: needs 2-D fp32 / bf16 rows of 1..128 channels and 1..8 steps (got %s %s, %d steps)"
+                       % (tuple(x.shape), x.dtype, steps))
+    C = x.shape[1]
+    for name, t, shape in (("w_ih", w_ih, (4 * C, 2 * C)), ("w_hh", w_hh, (4 * C, C)), ("b_ih", b_ih, (4 * C,)), ("b_hh", b_hh, (4 * C,))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise MdlError("set2set: %s must be fp32 %s (got %s %s)" % (name, shape, t.dtype, tuple(t.shape)))
+    if seg_index.perm is not None or seg_index.E != x.shape[0]:
+        raise MdlError("set2set: the segment index must be that of a sorted index over the %d rows of x" % x.shape[0])
+    return _Set2Set.apply(x, seg_index, w_ih, w_hh, b_ih, b_hh, int(steps))
 
 
 # ------------------------------------------------------------------------------------------------
