@@ -682,6 +682,28 @@ int mdl_set2set_bwd(const void* x, const int32_t* rowptr, const float* w_ih, con
                     const float* c, const float* q, const float* r, const float* a, float* da_ws, void* dx, float* dG, int64_t N,
                     int64_t S, int C, int T, int dtype, mdlStream_t stream);
 
+/* ---- Relaxation: one FIRE update of a batch of structures (csrc/relax.hip) --------------------
+ * No reference counterpart (the reference has no force path and moves no atoms).  FIRE (Bitzek et al. 2006) with unit masses,
+ * one workgroup per structure, ONE launch for the whole batch, all arithmetic fp64.  Atoms of structure b: rows node_ptr[b] ..
+ * node_ptr[b + 1] - 1 (node_ptr [B + 1] int64, clamped to [0, N]).
+ *   pos, vel [N, 3] fp64, in / out;  force [N, 3] fp32, read;  fixed [N] uint8 or NULL (non-zero: the atom does not move; its
+ *   force counts as zero, its velocity is written as zero);  fmax [B] fp64, read.
+ *   state, [B] each, in / out: dt, alpha fp64; n_pos, steps, done int32;  fmax_seen [B] fp32, written by every call.
+ * Structure b, f = the force with the rows of fixed atoms zeroed:
+ *   1. fm = max_i |f_i| (2-norm per atom); fmax_seen[b] = fm.  Converged if done[b] != 0, fm < fmax[b], or fm == 0 (no free atom,
+ *      no atom at all): done[b] = 1 and NOTHING else of the structure is written.
+ *   2. else, unless steps[b] == 0 (first step: no mixing; dt, alpha, n_pos kept), with P = sum f.v:
+ *      P > 0:  v <- (1 - alpha) v + alpha (|v| / |f|) f (norms over the structure); if n_pos > n_min: dt <- min(dt f_inc, dt_max),
+ *              alpha <- alpha f_alpha; then n_pos += 1
+ *      else:   v <- 0, alpha <- alpha_start, dt <- dt f_dec, n_pos <- 0
+ *   3. v <- v + dt f;  dr = dt v, scaled by maxstep / |dr| where |dr| (norm over the structure) > maxstep;  pos += dr;  steps += 1.
+ * Sums by wave shuffles, then the waves through LDS in wave order: no atomics, bitwise repeatable.  Caller owns every buffer; no
+ * allocation, no synchronisation.  B == 0 or N == 0 returns 0 without a launch. */
+int mdl_fire_step(double* pos, double* vel, const float* force, const uint8_t* fixed, const int64_t* node_ptr, int64_t N,
+                  int64_t B, const double* fmax, double* dt, double* alpha, int32_t* n_pos, int32_t* steps, int32_t* done,
+                  float* fmax_seen, int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double dt_max,
+                  double maxstep, mdlStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,7 @@ PROTOTYPES = {
     "mdl_set2set_supported": (_i32, [_i32, _i32, _i32]),
     "mdl_set2set_fwd": (_i32, [_vp] * 12 + [_i64, _i64, _i32, _i32, _i32, _vp]),
     "mdl_set2set_bwd": (_i32, [_vp] * 13 + [_i64, _i64, _i32, _i32, _i32, _vp]),
+    "mdl_fire_step": (_i32, [_vp] * 5 + [_i64, _i64] + [_vp] * 7 + [_i32] + [ctypes.c_double] * 6 + [_vp]),
 }
 
 _lib = None

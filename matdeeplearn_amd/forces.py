@@ -21,7 +21,12 @@ The derivative w.r.t. the cell (energy_forces_stress): at fixed neighbour lists 
 edge displacement v to (I + eps) v, and d|v|/d eps_ab = v_a v_b / |v|, so dE/d eps_ab of structure b = sum over its edges of
 (dE/dd_e) d_e u_e,a u_e,b — one reduction (ops.edge_strain_grad, csrc/edge_geom.hip) over the gradient w.r.t. the distances that
 the same backward already forms, not a second derivative chain.
-No second derivatives (training on forces): every backward is once_differentiable."""
+No second derivatives (training on forces): every backward is once_differentiable.
+Consumers of the forces: ForceField keeps the packed structures, the atom features and the neighbour lists on the device across
+calls (the host pass above happens once), and relax moves the atoms downhill with it — one batched FIRE update per step in one
+launch (ops.fire_step, csrc/relax.hip), every structure with its own time step and its own convergence latch."""
+import collections
+
 import numpy as np
 import torch
 
@@ -43,18 +48,27 @@ def _host(a, dtype):
     return np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=dtype)
 
 
-def _node_features(numbers, out_deg, max_neighbors, dictionary, dev):
-    """x = [atom features | one-hot out-degree incl. the self loop], as process.dataset._from_structures_device builds it"""
+def _atom_block(numbers, dictionary, dev):
+    """the atom-table rows of x, gathered once per atom (the only part of x that needs the host: np.unique over Z)"""
     z = np.asarray(numbers, dtype=np.int64)
     uz = np.unique(z)
     if dictionary is not None:                                 # one table row per distinct Z (graph.atom_features)
         table = np.asarray([dictionary[str(int(v))] for v in uz], dtype=np.float32)
     else:
         table = pg.atom_features(uz)
-    feats = torch.from_numpy(table).to(dev).index_select(0, torch.from_numpy(np.searchsorted(uz, z)).to(dev))
-    deg = torch.zeros((len(z), max_neighbors + 2), dtype=torch.float32, device=dev)
+    return torch.from_numpy(table).to(dev).index_select(0, torch.from_numpy(np.searchsorted(uz, z)).to(dev))
+
+
+def _with_degree_block(feats, out_deg, max_neighbors):
+    """x = [atom features | one-hot out-degree incl. the self loop]: the degree block follows the neighbour lists, on the device"""
+    deg = torch.zeros((feats.shape[0], max_neighbors + 2), dtype=torch.float32, device=feats.device)
     deg.scatter_(1, out_deg.long().unsqueeze(1), 1.0)
     return torch.cat([feats, deg], 1)
+
+
+def _node_features(numbers, out_deg, max_neighbors, dictionary, dev):
+    """x = [atom features | one-hot out-degree incl. the self loop], as process.dataset._from_structures_device builds it"""
+    return _with_degree_block(_atom_block(numbers, dictionary, dev), out_deg, max_neighbors)
 
 
 def energy_and_forces(model, structs, dist_range, radius=8.0, max_neighbors=12, dictionary=None, output_index=None, fused=True,
@@ -100,47 +114,78 @@ def energy_forces_stress(model, structs, dist_range, radius=8.0, max_neighbors=1
     pred, gpos, strain, node_ptr, (cell, pbc) = _energy_gradients(model, structs, dist_range, radius, max_neighbors, dictionary, output_index,
                                                                   fused, routes, True)
     if volume_normalised:
-        a, b, c = cell[:, 0], cell[:, 1], cell[:, 2]
-        vol = (a[:, 0] * (b[:, 1] * c[:, 2] - b[:, 2] * c[:, 1]) + a[:, 1] * (b[:, 2] * c[:, 0] - b[:, 0] * c[:, 2])
-               + a[:, 2] * (b[:, 0] * c[:, 1] - b[:, 1] * c[:, 0])).abs()
-        periodic = (pbc != 0).all(1) if pbc.dim() == 2 else (pbc & 7) == 7
-        has_volume = periodic & (vol > 0)
-        inv = torch.where(has_volume, 1.0 / torch.where(has_volume, vol, torch.ones_like(vol)), torch.full_like(vol, float("nan")))
-        strain = (strain.double() * inv.view(-1, 1, 1)).float()
+        strain = _per_volume(strain, cell, pbc)
     return pred, (-gpos).float(), strain, node_ptr
 
 
-def _energy_gradients(model, structs, dist_range, radius, max_neighbors, dictionary, output_index, fused, routes, want_strain):
-    """The body of energy_and_forces / energy_forces_stress: (pred, dE/dpos, dE/d eps [B, 3, 3] or None, node_ptr, (cell, pbc))"""
+def _per_volume(strain, cell, pbc):
+    """dE/d eps [B, 3, 3] -> stress: divided by the fp64 cell volume; NaN rows where a structure has no volume or is not periodic"""
+    a, b, c = cell[:, 0], cell[:, 1], cell[:, 2]
+    vol = (a[:, 0] * (b[:, 1] * c[:, 2] - b[:, 2] * c[:, 1]) + a[:, 1] * (b[:, 2] * c[:, 0] - b[:, 0] * c[:, 2])
+           + a[:, 2] * (b[:, 0] * c[:, 1] - b[:, 1] * c[:, 0])).abs()
+    periodic = (pbc != 0).all(1) if pbc.dim() == 2 else (pbc & 7) == 7
+    has_volume = periodic & (vol > 0)
+    inv = torch.where(has_volume, 1.0 / torch.where(has_volume, vol, torch.ones_like(vol)), torch.full_like(vol, float("nan")))
+    return (strain.double() * inv.view(-1, 1, 1)).float()
+
+
+def _accepted(model, dist_range):
+    """The checks every entry point starts with: (device, lo, hi) of an accepted model on a HIP device and a usable dist_range"""
     from .models import CGCNN, MEGNet, MPNN, SchNet
     if not isinstance(model, (CGCNN, SchNet, MEGNet, MPNN)):
         raise ops.MdlError("energy_and_forces: forces are implemented for CGCNN and SchNet, MEGNet and MPNN (got %s); GCN's edge "
                            "weight is the raw distance inside a degree normalisation, which has no distance gradient here "
                            "(DESIGN.md)" % type(model).__name__)
-    schnet = isinstance(model, SchNet)
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise ops.MdlError("energy_and_forces: the model must be a CGCNN, SchNet, MEGNet or MPNN on a HIP device (got %s)" % dev)
     lo, hi = float(dist_range[0]), float(dist_range[1])
     if not hi > lo:
         raise ops.MdlError("energy_and_forces: dist_range must be (min, max) with max > min")
+    return dev, lo, hi
+
+
+def _upload(p, dev):
+    """positions, node_ptr, cell and pbc of packed structures as device tensors"""
+    return (torch.from_numpy(_host(p["pos"], np.float64)).to(dev), torch.from_numpy(_host(p["node_ptr"], np.int64)).to(dev),
+            torch.from_numpy(_host(p["cell"], np.float64)).to(dev), torch.from_numpy(_host(p["pbc"], np.int32)).to(dev))
+
+
+def _held_lists(graphs, node_ptr, N):
+    """What a force evaluation holds fixed, from ops.build_graphs' result: batch-global (src, tgt), their EdgeCSR and out_deg"""
+    edge_ptr, src, tgt, _, out_deg = graphs
+    E = src.numel()
+    shift = torch.repeat_interleave(node_ptr[:-1], edge_ptr[1:] - edge_ptr[:-1], output_size=E).to(torch.int32)
+    src, tgt = (src + shift).contiguous(), (tgt + shift).contiguous()              # batch-global ids, CSR by target
+    return src, tgt, ops.EdgeCSR(ops.csr_rowptr(tgt, N), src, tgt, None, N, E), out_deg
+
+
+def _batch_index(node_ptr, N):
+    B = node_ptr.numel() - 1
+    return torch.repeat_interleave(torch.arange(B, device=node_ptr.device), node_ptr[1:] - node_ptr[:-1], output_size=N)
+
+
+def _energy_gradients(model, structs, dist_range, radius, max_neighbors, dictionary, output_index, fused, routes, want_strain):
+    """The body of energy_and_forces / energy_forces_stress: (pred, dE/dpos, dE/d eps [B, 3, 3] or None, node_ptr, (cell, pbc))"""
+    dev, lo, hi = _accepted(model, dist_range)
     p = _packed(structs)
-    pos = torch.from_numpy(_host(p["pos"], np.float64)).to(dev)
-    node_ptr = torch.from_numpy(_host(p["node_ptr"], np.int64)).to(dev)
-    cell = torch.from_numpy(_host(p["cell"], np.float64)).to(dev)
-    pbc = torch.from_numpy(_host(p["pbc"], np.int32)).to(dev)
-    N, B = pos.shape[0], node_ptr.numel() - 1
-
+    pos, node_ptr, cell, pbc = _upload(p, dev)
+    N = pos.shape[0]
     with torch.no_grad():
-        edge_ptr, src, tgt, _, out_deg = ops.build_graphs(pos, node_ptr, cell, pbc, radius, max_neighbors)
-        E = src.numel()
-        ncnt = node_ptr[1:] - node_ptr[:-1]
-        shift = torch.repeat_interleave(node_ptr[:-1], edge_ptr[1:] - edge_ptr[:-1], output_size=E).to(torch.int32)
-        src, tgt = (src + shift).contiguous(), (tgt + shift).contiguous()          # batch-global ids, CSR by target
-        csr = ops.EdgeCSR(ops.csr_rowptr(tgt, N), src, tgt, None, N, E)
+        src, tgt, csr, out_deg = _held_lists(ops.build_graphs(pos, node_ptr, cell, pbc, radius, max_neighbors), node_ptr, N)
         x = _node_features(_host(p["numbers"], np.int64), out_deg, int(max_neighbors), dictionary, dev)
-        batch_idx = torch.repeat_interleave(torch.arange(B, device=dev), ncnt, output_size=N)
+        batch_idx = _batch_index(node_ptr, N)
+    pred, gpos, strain = _device_gradients(model, pos, node_ptr, cell, pbc, src, tgt, csr, x, batch_idx, lo, hi, output_index, fused, routes,
+                                           want_strain)
+    return pred, gpos, strain, node_ptr, (cell, pbc)
 
+
+def _device_gradients(model, pos, node_ptr, cell, pbc, src, tgt, csr, x, batch_idx, lo, hi, output_index, fused, routes, want_strain):
+    """The device half both paths share: (pred, dE/dpos, dE/d eps [B, 3, 3] or None) at the positions `pos` on the GIVEN neighbour
+    lists (src, tgt batch-global, csr their EdgeCSR) with the node features x.  Nothing here touches the host."""
+    from .models import MEGNet, MPNN, SchNet
+    schnet = isinstance(model, SchNet)
+    dev, N, B, E = pos.device, pos.shape[0], node_ptr.numel() - 1, src.numel()
     with torch.enable_grad():
         pos_g = pos.detach().requires_grad_(True)
         if want_strain:
@@ -184,4 +229,141 @@ def _energy_gradients(model, structs, dist_range, radius, max_neighbors, diction
             if gdist is None:
                 gdist = torch.zeros_like(dist)
             strain = ops.edge_strain_grad(gdist, dist.detach(), unit, node_ptr, csr=csr)
-    return pred.detach(), gpos, strain, node_ptr, (cell, pbc)
+    return pred.detach(), gpos, strain
+
+
+class ForceField:
+    """The force chain of energy_and_forces, resident on the device: structures are packed and uploaded ONCE, the neighbour lists
+    are an object that is HELD across calls and rebuilt on request, and an evaluation touches the host nowhere.
+
+        ff = ForceField(model, structs, dist_range)      # arguments as energy_and_forces; builds the first lists
+        ff.positions     [N, 3] float64, the live positions (a device tensor; written in place by set_positions and by relax)
+        ff.node_ptr      [B + 1] int64;  ff.cell [B, 3, 3] float64;  ff.pbc [B] int32
+        ff.edges         (src, tgt) int32, batch-global, of the lists currently held
+        ff.set_positions(p)    new positions; the lists are NOT touched
+        ff.rebuild()           neighbour lists, their CSR and the out-degree block of x from the current positions, on the device
+                               (one number, the edge count, is read back)
+        ff.evaluate(stress=False)   (pred, forces [N, 3] fp32[, stress [B, 3, 3] fp32]) at the current positions ON THE HELD LISTS
+
+    Right after construction or a rebuild(), evaluate() returns the bits of energy_and_forces / energy_forces_stress on structures
+    at ff.positions (the same launches on the same operands).  Between rebuilds the energy is the smooth function whose derivative
+    the forces are: an atom that would enter or leave a list under the displacement does not; the minimum image of every held edge
+    is still chosen anew from the positions.  The model's CURRENT mode is used, as in energy_and_forces."""
+
+    def __init__(self, model, structs, dist_range, radius=8.0, max_neighbors=12, dictionary=None, output_index=None, fused=True):
+        self._dev, self._lo, self._hi = _accepted(model, dist_range)
+        self.model, self.radius, self.max_neighbors = model, float(radius), int(max_neighbors)
+        self.output_index, self.fused = output_index, bool(fused)
+        p = _packed(structs)
+        node_ptr = _host(p["node_ptr"], np.int64)
+        n_atoms = _host(p["pos"], np.float64).shape[0]
+        if n_atoms < 1:
+            raise ops.MdlError("build_graphs: no atoms")
+        if node_ptr.ndim != 1 or node_ptr.size < 2 or node_ptr[0] != 0 or node_ptr[-1] != n_atoms or (np.diff(node_ptr) < 0).any():
+            raise ops.MdlError("build_graphs: node_ptr must start at 0, be non-decreasing and end at N = %d" % n_atoms)
+        self.positions, self.node_ptr, self.cell, self.pbc = _upload(p, self._dev)
+        self._atoms = _atom_block(_host(p["numbers"], np.int64), dictionary, self._dev)
+        self._batch = _batch_index(self.node_ptr, n_atoms)
+        self.rebuild()
+
+    @property
+    def edges(self):
+        return self._src, self._tgt
+
+    def set_positions(self, positions):
+        """Overwrite the live positions ([N, 3], a device tensor or anything numpy reads).  The neighbour lists stay as they are."""
+        p = positions if torch.is_tensor(positions) else torch.from_numpy(np.asarray(positions, dtype=np.float64))
+        if tuple(p.shape) != tuple(self.positions.shape):
+            raise ops.MdlError("ForceField.set_positions: positions must be [N, 3] with N = %d (got %s)" % (self.positions.shape[0], tuple(p.shape)))
+        self.positions.copy_(p.detach())
+
+    def rebuild(self):
+        """Neighbour lists from the current positions (ops.build_graphs' launches), made batch-global, with their CSR and the
+        node features whose out-degree block follows them.  Reads the edge count back; nothing else crosses to the host."""
+        with torch.no_grad():
+            pos, node_ptr, cell, pbc, G = ops._graph_args(self.positions, self.node_ptr, self.cell, self.pbc)
+            edge_ptr, src, tgt, dist, out_deg = ops._build_graphs_launch(pos, node_ptr, cell, pbc, G, self.radius, self.max_neighbors)
+            E = int(edge_ptr[-1])
+            self._src, self._tgt, self._csr, _ = _held_lists((edge_ptr, src[:E], tgt[:E], None, out_deg), node_ptr, pos.shape[0])
+            self._x = _with_degree_block(self._atoms, out_deg, self.max_neighbors)
+
+    def evaluate(self, stress=False, volume_normalised=True):
+        """(pred [B] or [B, out] fp32, forces [N, 3] fp32) at the current positions on the held lists; with stress=True also
+        stress [B, 3, 3] fp32 as energy_forces_stress defines it (volume_normalised=False: dE/d eps itself)."""
+        pred, gpos, strain = _device_gradients(self.model, self.positions, self.node_ptr, self.cell, self.pbc, self._src, self._tgt, self._csr,
+                                               self._x, self._batch, self._lo, self._hi, self.output_index, self.fused,
+                                               ("expansion", "cutoff"), bool(stress))
+        if not stress:
+            return pred, (-gpos).float()
+        return pred, (-gpos).float(), _per_volume(strain, self.cell, self.pbc) if volume_normalised else strain
+
+
+RelaxResult = collections.namedtuple("RelaxResult", "positions energy forces converged steps fmax node_ptr")
+
+
+def relax(model, structs, dist_range, fmax=0.05, steps=200, rebuild_every=1, fixed=None, dt=0.1, dt_max=1.0, maxstep=0.2, n_min=5,
+          f_inc=1.1, f_dec=0.5, alpha=0.1, f_alpha=0.99, check_every=10, radius=8.0, max_neighbors=12, dictionary=None,
+          output_index=None):
+    """Move the atoms of a batch of structures downhill in the model's prediction: FIRE (unit masses) on the forces of a
+    ForceField, every structure with its own time step and its own convergence, the whole step on the device.
+
+    model, structs, dist_range, radius, max_neighbors, dictionary, output_index   as energy_and_forces; the model must be in
+                  eval() (training-mode BatchNorm couples the structures of a batch: a converged structure would keep moving
+                  in energy with the others) — MdlError otherwise
+    fmax          a structure is converged once its largest per-atom force is below this (a number, or one per structure); it is
+                  then frozen: its positions keep their bits while the others go on
+    steps         at most this many updates
+    rebuild_every 0: the neighbour lists of the initial positions are held throughout (the energy is one smooth function);
+                  n >= 1: the lists are rebuilt before every n-th evaluation, the final one included
+    fixed         [N] mask (tensor or array, non-zero: the atom does not move), or None
+    dt, dt_max, maxstep, n_min, f_inc, f_dec, alpha, f_alpha   FIRE's constants (ops.fire_step; alpha is also alpha_start);
+                  maxstep bounds the norm of a structure's whole displacement per step
+    check_every   the loop asks the device whether every structure is done every this many steps (the only host read besides
+                  the edge count at a rebuild); 0: never, all `steps` updates are launched
+
+    Positions are not wrapped into the cell (the minimum image does not need it).  After the last update the forces are evaluated
+    once more, so energy, forces and fmax belong to the returned positions on the lists then in force.
+    Returns RelaxResult(positions [N, 3] float64, energy [B] or [B, out] fp32, forces [N, 3] fp32, converged [B] bool, steps [B]
+    int32 (updates made per structure), fmax [B] fp32 (largest per-atom force on a free atom), node_ptr), device tensors.  With
+    ops.deterministic() two calls return the same bits: the integrator itself has no atomics."""
+    _accepted(model, dist_range)
+    if model.training:
+        raise ops.MdlError("relax: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
+                           "(and dropout makes the energy a random function)")
+    steps, rebuild_every, check_every = int(steps), int(rebuild_every), int(check_every)
+    if steps < 0 or rebuild_every < 0 or check_every < 0:
+        raise ops.MdlError("relax: steps, rebuild_every and check_every must be >= 0")
+    ff = ForceField(model, structs, dist_range, radius, max_neighbors, dictionary, output_index)
+    dev, N, B = ff.positions.device, ff.positions.shape[0], ff.node_ptr.numel() - 1
+    if torch.is_tensor(fmax) or np.ndim(fmax) > 0:
+        fmax_t = (fmax.detach() if torch.is_tensor(fmax) else torch.from_numpy(np.asarray(fmax, dtype=np.float64))).to(dev, torch.float64)
+        if tuple(fmax_t.shape) != (B,):
+            raise ops.MdlError("relax: fmax must be a number or one value per structure, [%d] (got %s)" % (B, tuple(fmax_t.shape)))
+    else:
+        fmax_t = torch.full((B,), float(fmax), dtype=torch.float64, device=dev)
+    if fixed is not None:
+        fixed = (fixed.detach() if torch.is_tensor(fixed) else torch.from_numpy(np.asarray(fixed))).to(dev)
+        if tuple(fixed.shape) != (N,):
+            raise ops.MdlError("relax: fixed must be an [N] mask with N = %d (got %s)" % (N, tuple(fixed.shape)))
+        fixed = (fixed != 0).to(torch.uint8)
+    const = dict(n_min=n_min, f_inc=f_inc, f_dec=f_dec, alpha_start=alpha, f_alpha=f_alpha, dt_max=dt_max, maxstep=maxstep)
+    state = ops.fire_state(B, dt, alpha, dev)
+    vel = torch.zeros_like(ff.positions)
+    n_eval = 0
+    for it in range(steps):
+        if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
+            ff.rebuild()
+        _, f = ff.evaluate()
+        n_eval += 1
+        ops.fire_step(ff.positions, vel, f, ff.node_ptr, state, fmax_t, fixed, **const)
+        if check_every > 0 and (it + 1) % check_every == 0 and bool(state.done.all()):
+            break
+    if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
+        ff.rebuild()
+    energy, f = ff.evaluate()
+    # the largest force at the returned positions, from the integrator's own pass 1: with every latch set nothing else is written
+    probe = state.clone()
+    probe.done.fill_(1)
+    ops.fire_step(ff.positions, vel, f, ff.node_ptr, probe, fmax_t, fixed, **const)
+    converged = (state.done != 0) | (probe.fmax_seen.double() < fmax_t)
+    return RelaxResult(ff.positions, energy, f, converged, state.steps, probe.fmax_seen, ff.node_ptr)

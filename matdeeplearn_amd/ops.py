@@ -2743,3 +2743,81 @@ def edge_strain_grad(g_dist, dist, u, node_ptr, csr=None, src=None, tgt=None, _s
                                      ptr(csr.rowptr), ptr(csr.eperm), ptr(node_ptr.contiguous()), csr.N, G, E, S, ptr(out), ptr(ws),
                                      nbytes, stream()), "mdl_edge_strain_grad")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Relaxation: one FIRE update of a batch of structures in one launch (csrc/relax.hip)
+# ------------------------------------------------------------------------------------------------
+FIRE_CONSTANTS = {"n_min": 5, "f_inc": 1.1, "f_dec": 0.5, "alpha_start": 0.1, "f_alpha": 0.99, "dt_max": 1.0, "maxstep": 0.2}
+
+
+class FireState:
+    """Per-structure state of fire_step, [B] device tensors: dt, alpha float64; n_pos (steps with F.v > 0 in a row), steps (updates
+    made) and done (the convergence latch) int32; fmax_seen float32, the max_i |F_i| every call writes."""
+
+    __slots__ = ("dt", "alpha", "n_pos", "steps", "done", "fmax_seen")
+
+    def __init__(self, dt, alpha, n_pos, steps, done, fmax_seen):
+        self.dt, self.alpha, self.n_pos, self.steps, self.done, self.fmax_seen = dt, alpha, n_pos, steps, done, fmax_seen
+
+    def clone(self):
+        return FireState(*[getattr(self, k).clone() for k in self.__slots__])
+
+
+def fire_state(B, dt=0.1, alpha=0.1, device=None):
+    """A fresh FireState of B structures: time step dt, mixing alpha, no step made, nothing converged."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    zi = lambda: torch.zeros(int(B), dtype=torch.int32, device=dev)
+    return FireState(torch.full((int(B),), float(dt), dtype=torch.float64, device=dev),
+                     torch.full((int(B),), float(alpha), dtype=torch.float64, device=dev), zi(), zi(), zi(),
+                     torch.zeros(int(B), dtype=torch.float32, device=dev))
+
+
+def fire_step(pos, vel, force, node_ptr, state, fmax, fixed=None, **constants):
+    """One FIRE update (unit masses) of every structure of a batch, in place, in ONE launch.
+      pos, vel [N, 3] float64 (updated in place: contiguous tensors), force [N, 3] float32, node_ptr [B + 1] int64, state a
+      FireState of B structures (updated in place), fmax a number or a [B] float64 tensor, fixed [N] uint8 / bool or None
+      (non-zero: the atom stays where it is), constants: any of FIRE_CONSTANTS (n_min, f_inc, f_dec, alpha_start, f_alpha,
+      dt_max, maxstep).
+    A structure whose largest per-atom force is below its fmax — or that converged in an earlier call, or has no force on a free
+    atom — gets state.done = 1 and is otherwise left alone: positions, velocities and the rest of its state keep their bits.
+    The others move as include/mdl_hip.h (mdl_fire_step) states it.  No host synchronisation, no atomics: two calls from the same
+    inputs give the same bits.  Returns state."""
+    unknown = set(constants) - set(FIRE_CONSTANTS)
+    if unknown:
+        raise MdlError("fire_step: unknown constants %s (known: %s)" % (sorted(unknown), sorted(FIRE_CONSTANTS)))
+    c = dict(FIRE_CONSTANTS, **constants)
+    if not isinstance(state, FireState):
+        raise MdlError("fire_step: state must be an ops.FireState (ops.fire_state)")
+    require_hip(pos, vel, force, node_ptr, fixed, *[getattr(state, k) for k in FireState.__slots__])
+    N = pos.shape[0] if pos.dim() == 2 else -1
+    for name, t in (("pos", pos), ("vel", vel)):
+        if t.dtype != torch.float64 or tuple(t.shape) != (N, 3) or not t.is_contiguous():
+            raise MdlError("fire_step: %s must be a contiguous [N, 3] float64 tensor (got %s %s)" % (name, tuple(t.shape), t.dtype))
+    if force.dtype != torch.float32 or tuple(force.shape) != (N, 3):
+        raise MdlError("fire_step: force must be [N, 3] float32 with N = %d (got %s %s)" % (N, tuple(force.shape), force.dtype))
+    if node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 1:
+        raise MdlError("fire_step: node_ptr must be [B + 1] int64")
+    B = node_ptr.numel() - 1
+    for k, dt_ in (("dt", torch.float64), ("alpha", torch.float64), ("n_pos", torch.int32), ("steps", torch.int32), ("done", torch.int32),
+                   ("fmax_seen", torch.float32)):
+        t = getattr(state, k)
+        if t.dtype != dt_ or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise MdlError("fire_step: state.%s must be a contiguous [B] %s tensor with B = %d (got %s %s)" % (k, dt_, B, tuple(t.shape), t.dtype))
+    if torch.is_tensor(fmax):
+        if fmax.dtype != torch.float64 or tuple(fmax.shape) != (B,):
+            raise MdlError("fire_step: fmax must be a number or a [B] float64 tensor with B = %d (got %s %s)" % (B, tuple(fmax.shape), fmax.dtype))
+        require_hip(fmax)
+    else:
+        fmax = torch.full((B,), float(fmax), dtype=torch.float64, device=pos.device)
+    if fixed is not None:
+        if fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
+            raise MdlError("fire_step: fixed must be [N] uint8 or bool with N = %d (got %s %s)" % (N, tuple(fixed.shape), fixed.dtype))
+        fixed = fixed.contiguous().view(torch.uint8)
+    if any(t.device != pos.device for t in (vel, force, node_ptr, fmax, state.dt) if t is not None):
+        raise MdlError("fire_step: pos, vel, force, node_ptr, fmax and the state must be on one device")
+    check(lib().mdl_fire_step(ptr(pos), ptr(vel), ptr(force.contiguous()), ptr(fixed), ptr(node_ptr.contiguous()), N, B, ptr(fmax.contiguous()),
+                              ptr(state.dt), ptr(state.alpha), ptr(state.n_pos), ptr(state.steps), ptr(state.done), ptr(state.fmax_seen),
+                              int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
+                              float(c["dt_max"]), float(c["maxstep"]), stream()), "mdl_fire_step")
+    return state
