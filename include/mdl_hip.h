@@ -704,6 +704,37 @@ int mdl_fire_step(double* pos, double* vel, const float* force, const uint8_t* f
                   float* fmax_seen, int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double dt_max,
                   double maxstep, mdlStream_t stream);
 
+/* mdl_fire_cell_step: the same update over the atoms AND the cell of every structure, N + 3 rows per structure, ONE launch.
+ * Cells are row-vector matrices.  C0 = cell0[b] is the cell the relaxation started from; the deformation gradient F = deform[b]
+ * is defined by cell[b] = C0 F^T, so every lattice vector is a_k = F a0_k and atom i sits at pos_i = F s_i (s = scaled).  The
+ * degrees of freedom are the rows s_i and the three rows of W = cf F, cf = cell_factor[b] > 0.  Generalised forces (f_i the
+ * Cartesian force with the rows of fixed atoms zeroed, S = strain_grad[b] = dE/d eps of the structure, NOT divided by the volume):
+ *      on s_i:  F^T f_i          on W:  -(1 / cf) S F^-T        (F^-1 through the adjugate)
+ *   pos, scaled, vel [N, 3] fp64 and cell, deform, vel_cell [B, 3, 3] fp64, in / out (vel, vel_cell: the velocities of s and W);
+ *   force [N, 3] fp32, strain_grad [B, 3, 3] fp32, cell0 [B, 3, 3] fp64, fixed [N] uint8 or NULL, cell_free [B] uint8,
+ *   cell_factor, fmax, smax [B] fp64, read;  the state of mdl_fire_step plus smax_seen [B] fp32, written by every call.
+ * Structure b:
+ *   1. fm = max_i |f_i| (Cartesian), sm = max_ab |S_ab| / |det cell[b]| (NaN where the cell has no volume); fmax_seen[b] = fm,
+ *      smax_seen[b] = sm.  If done[b] != 0 it stays what it is.  Else, if (fm < fmax[b] or !(fm > 0)) and (cell_free[b] == 0 or
+ *      sm < smax[b] or !(sm > 0)): done[b] = 1.  In both cases NOTHING else of the structure is written.
+ *   2. steps 2 and 3 of mdl_fire_step with the generalised forces and velocities of all N + 3 rows: |g|^2, g.v, |v|^2 and the
+ *      norm of the displacement that maxstep bounds are sums over the atoms' rows plus the cell's rows.
+ *   3. s_i += clip dt v_i (free atoms), W += clip dt v_W, F' = W / cf.  If !(|F' - I|_Frobenius <= max_deform) — too far, or a
+ *      non-finite entry — done[b] = 2 and nothing else of this update is written: the geometry stays the last accepted one.
+ *      Else deform = F', pos_i = F' s_i for EVERY atom (fixed atoms keep s_i and ride with the cell; their velocity is written
+ *      as zero), cell = C0 F'^T, velocities and state as mdl_fire_step, steps += 1.  0 < max_deform < 1 bounds the smallest
+ *      singular value of every F the caller can see from below by 1 - max_deform: no accepted cell is degenerate.
+ *   cell_free[b] == 0: the cell rows contribute nothing, F is taken as I; pos, vel and the state get the bits of mdl_fire_step
+ *      on the same inputs, scaled gets the bits of pos, and cell, deform and vel_cell of b are not written.
+ * The 3x3 algebra is done by every lane from the same values; lane 0 alone reads and writes what is per structure.  Sums as in
+ * mdl_fire_step: no atomics, bitwise repeatable.  Argument checks of mdl_fire_step plus 0 < max_deform < 1. */
+int mdl_fire_cell_step(double* pos, double* cell, double* scaled, double* deform, double* vel, double* vel_cell, const float* force,
+                       const float* strain_grad, const double* cell0, const uint8_t* fixed, const uint8_t* cell_free,
+                       const double* cell_factor, const int64_t* node_ptr, int64_t N, int64_t B, const double* fmax, const double* smax,
+                       double* dt, double* alpha, int32_t* n_pos, int32_t* steps, int32_t* done, float* fmax_seen, float* smax_seen,
+                       int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double dt_max, double maxstep,
+                       double max_deform, mdlStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

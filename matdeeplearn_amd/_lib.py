@@ -149,6 +149,7 @@ PROTOTYPES = {
     "mdl_set2set_fwd": (_i32, [_vp] * 12 + [_i64, _i64, _i32, _i32, _i32, _vp]),
     "mdl_set2set_bwd": (_i32, [_vp] * 13 + [_i64, _i64, _i32, _i32, _i32, _vp]),
     "mdl_fire_step": (_i32, [_vp] * 5 + [_i64, _i64] + [_vp] * 7 + [_i32] + [ctypes.c_double] * 6 + [_vp]),
+    "mdl_fire_cell_step": (_i32, [_vp] * 13 + [_i64, _i64] + [_vp] * 9 + [_i32] + [ctypes.c_double] * 7 + [_vp]),
 }
 
 _lib = None

@@ -24,7 +24,9 @@ the same backward already forms, not a second derivative chain.
 No second derivatives (training on forces): every backward is once_differentiable.
 Consumers of the forces: ForceField keeps the packed structures, the atom features and the neighbour lists on the device across
 calls (the host pass above happens once), and relax moves the atoms downhill with it — one batched FIRE update per step in one
-launch (ops.fire_step, csrc/relax.hip), every structure with its own time step and its own convergence latch."""
+launch (ops.fire_step, csrc/relax.hip), every structure with its own time step and its own convergence latch.  relax_cell moves
+the cell with the atoms: the same update over the atoms' rows and the three rows of the deformation gradient, driven by the strain
+gradient of energy_forces_stress (ops.fire_cell_step), still one launch per step."""
 import collections
 
 import numpy as np
@@ -238,9 +240,12 @@ class ForceField:
 
         ff = ForceField(model, structs, dist_range)      # arguments as energy_and_forces; builds the first lists
         ff.positions     [N, 3] float64, the live positions (a device tensor; written in place by set_positions and by relax)
-        ff.node_ptr      [B + 1] int64;  ff.cell [B, 3, 3] float64;  ff.pbc [B] int32
+        ff.node_ptr      [B + 1] int64;  ff.cell [B, 3, 3] float64, the live cells (written in place by set_cell and by
+                         relax_cell);  ff.pbc [B] int32
         ff.edges         (src, tgt) int32, batch-global, of the lists currently held
         ff.set_positions(p)    new positions; the lists are NOT touched
+        ff.set_cell(c, scale_atoms=False)   new cells [B, 3, 3] (scale_atoms: the atoms keep their fractional coordinates); the
+                               lists are NOT touched
         ff.rebuild()           neighbour lists, their CSR and the out-degree block of x from the current positions, on the device
                                (one number, the edge count, is read back)
         ff.evaluate(stress=False)   (pred, forces [N, 3] fp32[, stress [B, 3, 3] fp32]) at the current positions ON THE HELD LISTS
@@ -276,6 +281,27 @@ class ForceField:
         if tuple(p.shape) != tuple(self.positions.shape):
             raise ops.MdlError("ForceField.set_positions: positions must be [N, 3] with N = %d (got %s)" % (self.positions.shape[0], tuple(p.shape)))
         self.positions.copy_(p.detach())
+
+    def set_cell(self, cell, scale_atoms=False):
+        """Overwrite the live cells ([B, 3, 3], rows are lattice vectors; a device tensor or anything numpy reads).  With
+        scale_atoms=True the atoms keep their fractional coordinates, pos <- pos C_old^-1 C_new per structure, on the device
+        (atoms of a structure whose old cell has no volume stay where they are).  The neighbour lists stay as they are."""
+        c = cell if torch.is_tensor(cell) else torch.from_numpy(np.asarray(cell, dtype=np.float64))
+        if tuple(c.shape) != tuple(self.cell.shape):
+            raise ops.MdlError("ForceField.set_cell: cell must be [B, 3, 3] with B = %d (got %s)" % (self.cell.shape[0], tuple(c.shape)))
+        new = c.detach().to(self.cell.device, torch.float64)
+        if scale_atoms:
+            with torch.no_grad():
+                o = self.cell
+                adj = torch.stack([torch.linalg.cross(o[:, 1], o[:, 2]), torch.linalg.cross(o[:, 2], o[:, 0]),
+                                   torch.linalg.cross(o[:, 0], o[:, 1])], 2)        # columns: b x c, c x a, a x b = det * C_old^-1
+                det = (o[:, 0] * adj[:, :, 0]).sum(1)
+                ok = det != 0
+                inv = adj / torch.where(ok, det, torch.ones_like(det)).view(-1, 1, 1)
+                eye = torch.eye(3, dtype=torch.float64, device=o.device).expand_as(o)
+                m = torch.where(ok.view(-1, 1, 1), torch.bmm(inv, new), eye)
+                self.positions.copy_(torch.bmm(self.positions.unsqueeze(1), m.index_select(0, self._batch)).squeeze(1))
+        self.cell.copy_(new)
 
     def rebuild(self):
         """Neighbour lists from the current positions (ops.build_graphs' launches), made batch-global, with their CSR and the
@@ -367,3 +393,100 @@ def relax(model, structs, dist_range, fmax=0.05, steps=200, rebuild_every=1, fix
     ops.fire_step(ff.positions, vel, f, ff.node_ptr, probe, fmax_t, fixed, **const)
     converged = (state.done != 0) | (probe.fmax_seen.double() < fmax_t)
     return RelaxResult(ff.positions, energy, f, converged, state.steps, probe.fmax_seen, ff.node_ptr)
+
+
+CellRelaxResult = collections.namedtuple("CellRelaxResult", "positions cell energy forces stress converged steps fmax smax status node_ptr")
+
+
+def _per_structure(v, B, dev, what):
+    """a number or one value per structure -> [B] float64 on the device"""
+    if torch.is_tensor(v) or np.ndim(v) > 0:
+        t = (v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, dtype=np.float64))).to(dev, torch.float64)
+        if tuple(t.shape) != (B,):
+            raise ops.MdlError("relax_cell: %s must be a number or one value per structure, [%d] (got %s)" % (what, B, tuple(t.shape)))
+        return t.contiguous()
+    return torch.full((B,), float(v), dtype=torch.float64, device=dev)
+
+
+def relax_cell(model, structs, dist_range, fmax=0.05, smax=1e-3, steps=200, rebuild_every=1, fixed=None, cell_free=None, cell_factor=None,
+               max_deform=0.5, dt=0.1, dt_max=1.0, maxstep=0.2, n_min=5, f_inc=1.1, f_dec=0.5, alpha=0.1, f_alpha=0.99, check_every=10,
+               radius=8.0, max_neighbors=12, dictionary=None, output_index=None):
+    """relax with the cell among the degrees of freedom: FIRE over the atoms and the cell of every structure, driven by the forces
+    and the strain gradient of a ForceField, the whole step on the device (ops.fire_cell_step: one launch).
+
+    Coordinates (include/mdl_hip.h, mdl_fire_cell_step): with C0 the cell at the start, the cell is C = C0 F^T and atom i sits at
+    F s_i; the integrator moves the rows s_i and the three rows of W = cell_factor F with the generalised forces F^T f_i and
+    -(1 / cell_factor) (dE/d eps) F^-T, mixing, time step and maxstep taken over all N + 3 rows of a structure together.
+
+    model, structs, dist_range, steps, rebuild_every, fixed, check_every, radius, max_neighbors, dictionary, output_index and
+    FIRE's constants   as relax (fixed atoms keep their s_i: they ride with the cell)
+    fmax, smax    a structure is converged once its largest per-atom force is below fmax AND, where its cell is free, the largest
+                  component of its stress, max_ab |dE/d eps_ab| / volume, is below smax (numbers, or one per structure).  smax is
+                  in the model's energy unit per cubic Angstrom: for a model trained on eV the default 1e-3 is 0.16 GPa
+    cell_free     [B] mask or None (every cell).  The cell of a structure moves only if the structure is periodic along all three
+                  axes, its cell has a volume and this mask allows it; every other structure is relaxed as relax does it (the
+                  same bits), and its cell comes back as it went in
+    cell_factor   [B] > 0 or None (max(1, atoms of the structure)): the weight of the cell's rows, see ops.fire_cell_state
+    max_deform    in (0, 1): the trust region.  An update that would take |F - I| (Frobenius) beyond it is not made; the structure
+                  stops at its last accepted geometry with status 2.  Every F a kernel sees therefore has a smallest singular
+                  value >= 1 - max_deform: no collapsing cell reaches the graph builder.  Restart from the result to go further
+
+    After the last update energy, forces and stress are evaluated once more, so they belong to the returned positions and cell on
+    the lists then in force.  Returns CellRelaxResult(positions [N, 3] float64, cell [B, 3, 3] float64, energy, forces [N, 3] fp32,
+    stress [B, 3, 3] fp32 (volume-normalised as energy_forces_stress returns it: NaN rows for structures without one), converged [B]
+    bool, steps [B] int32, fmax [B] fp32, smax [B] fp32 (max |stress| at the returned geometry; NaN where stress is), status [B]
+    int32 (0 still moving, 1 converged, 2 stopped by the trust region), node_ptr), device tensors.  With ops.deterministic() two
+    calls return the same bits."""
+    _accepted(model, dist_range)
+    if model.training:
+        raise ops.MdlError("relax_cell: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
+                           "(and dropout makes the energy a random function)")
+    steps, rebuild_every, check_every = int(steps), int(rebuild_every), int(check_every)
+    if steps < 0 or rebuild_every < 0 or check_every < 0:
+        raise ops.MdlError("relax_cell: steps, rebuild_every and check_every must be >= 0")
+    if not 0.0 < float(max_deform) < 1.0:
+        raise ops.MdlError("relax_cell: max_deform must be in (0, 1) (got %r)" % (max_deform,))
+    ff = ForceField(model, structs, dist_range, radius, max_neighbors, dictionary, output_index)
+    dev, N, B = ff.positions.device, ff.positions.shape[0], ff.node_ptr.numel() - 1
+    fmax_t, smax_t = _per_structure(fmax, B, dev, "fmax"), _per_structure(smax, B, dev, "smax")
+    if fixed is not None:
+        fixed = (fixed.detach() if torch.is_tensor(fixed) else torch.from_numpy(np.asarray(fixed))).to(dev)
+        if tuple(fixed.shape) != (N,):
+            raise ops.MdlError("relax_cell: fixed must be an [N] mask with N = %d (got %s)" % (N, tuple(fixed.shape)))
+        fixed = (fixed != 0).to(torch.uint8)
+    c = ff.cell
+    vol = (c[:, 0] * torch.linalg.cross(c[:, 1], c[:, 2])).sum(1).abs()
+    free = ((ff.pbc != 0).all(1) if ff.pbc.dim() == 2 else (ff.pbc & 7) == 7) & (vol > 0)
+    if cell_free is not None:
+        mask = (cell_free.detach() if torch.is_tensor(cell_free) else torch.from_numpy(np.asarray(cell_free))).to(dev)
+        if tuple(mask.shape) != (B,):
+            raise ops.MdlError("relax_cell: cell_free must be a [B] mask with B = %d (got %s)" % (B, tuple(mask.shape)))
+        free = free & (mask != 0)
+    if cell_factor is not None:
+        cell_factor = _per_structure(cell_factor, B, dev, "cell_factor")
+    const = dict(n_min=n_min, f_inc=f_inc, f_dec=f_dec, alpha_start=alpha, f_alpha=f_alpha, dt_max=dt_max, maxstep=maxstep,
+                 max_deform=max_deform)
+    state = ops.fire_cell_state(ff.positions, ff.cell, ff.node_ptr, free, cell_factor, dt, alpha)
+    vel = torch.zeros_like(ff.positions)
+    n_eval = 0
+    for it in range(steps):
+        if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
+            ff.rebuild()
+        _, f, strain = ff.evaluate(stress=True, volume_normalised=False)
+        n_eval += 1
+        ops.fire_cell_step(ff.positions, ff.cell, vel, f, strain, ff.node_ptr, state, fmax_t, smax_t, fixed, **const)
+        if check_every > 0 and (it + 1) % check_every == 0 and bool(state.done.all()):
+            break
+    if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
+        ff.rebuild()
+    energy, f, strain = ff.evaluate(stress=True, volume_normalised=False)
+    # the criteria at the returned geometry, from the integrator's own pass 1: with every latch set nothing else is written
+    probe = state.clone()
+    probe.done.fill_(1)
+    ops.fire_cell_step(ff.positions, ff.cell, vel, f, strain, ff.node_ptr, probe, fmax_t, smax_t, fixed, **const)
+    fm, sm = probe.fmax_seen.double(), probe.smax_seen.double()
+    met = ((fm < fmax_t) | ~(fm > 0)) & ((state.cell_free == 0) | (sm < smax_t) | ~(sm > 0))
+    converged = (state.done == 1) | met
+    stress = _per_volume(strain, ff.cell, ff.pbc)
+    smax_seen = torch.where(torch.isnan(stress).flatten(1).any(1), torch.full_like(probe.smax_seen, float("nan")), probe.smax_seen)
+    return CellRelaxResult(ff.positions, ff.cell, energy, f, stress, converged, state.steps, probe.fmax_seen, smax_seen, state.done, ff.node_ptr)

@@ -2821,3 +2821,120 @@ def fire_step(pos, vel, force, node_ptr, state, fmax, fixed=None, **constants):
                               int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
                               float(c["dt_max"]), float(c["maxstep"]), stream()), "mdl_fire_step")
     return state
+
+
+class FireCellState:
+    """Per-structure state of fire_cell_step: the FireState fields ([B]: dt, alpha, n_pos, steps, done, fmax_seen) and what the
+    cell's degrees of freedom add — scaled [N, 3] float64 (s: pos_i = F s_i), deform [B, 3, 3] float64 (F: cell = cell0 F^T),
+    vel_cell [B, 3, 3] float64 (the velocity of W = cell_factor F), cell0 [B, 3, 3] float64 (the cell at the start), cell_free [B]
+    uint8, cell_factor [B] float64, smax_seen [B] float32 (max |dE/d eps| / volume, written by every call).  done: 0 moving,
+    1 converged, 2 stopped by the trust region (|F - I| would have exceeded max_deform)."""
+
+    __slots__ = FireState.__slots__ + ("scaled", "deform", "vel_cell", "cell0", "cell_free", "cell_factor", "smax_seen")
+
+    def __init__(self, *fields):
+        if len(fields) != len(self.__slots__):
+            raise MdlError("FireCellState: %d fields (%s)" % (len(self.__slots__), ", ".join(self.__slots__)))
+        for k, v in zip(self.__slots__, fields):
+            setattr(self, k, v)
+
+    def clone(self):
+        return FireCellState(*[getattr(self, k).clone() for k in self.__slots__])
+
+
+_FIRE_CELL_FIELDS = (("dt", torch.float64, ()), ("alpha", torch.float64, ()), ("n_pos", torch.int32, ()), ("steps", torch.int32, ()),
+                     ("done", torch.int32, ()), ("fmax_seen", torch.float32, ()), ("deform", torch.float64, (3, 3)),
+                     ("vel_cell", torch.float64, (3, 3)), ("cell0", torch.float64, (3, 3)), ("cell_free", torch.uint8, ()),
+                     ("cell_factor", torch.float64, ()), ("smax_seen", torch.float32, ()))
+FIRE_CELL_CONSTANTS = dict(FIRE_CONSTANTS, max_deform=0.5)
+
+
+def fire_cell_state(pos, cell, node_ptr, cell_free=None, cell_factor=None, dt=0.1, alpha=0.1):
+    """A fresh FireCellState for the geometry (pos [N, 3], cell [B, 3, 3] float64, node_ptr [B + 1] int64, device tensors): s = a
+    copy of pos, F = I, no velocity of the cell, cell0 = a copy of cell, nothing converged.  cell_free [B] (non-zero: the cell of
+    the structure moves; default: every cell), cell_factor [B] > 0 (default max(1, atoms of the structure)): the cell's rows enter
+    as W = cell_factor F, so a strain of eps moves the integrator's coordinates as far as moving cell_factor atoms by eps each."""
+    require_hip(pos, cell, node_ptr)
+    if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 3:
+        raise MdlError("fire_cell_state: pos must be [N, 3] float64 (got %s %s)" % (tuple(pos.shape), pos.dtype))
+    if node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 1:
+        raise MdlError("fire_cell_state: node_ptr must be [B + 1] int64")
+    B, dev = node_ptr.numel() - 1, pos.device
+    if cell.dtype != torch.float64 or tuple(cell.shape) != (B, 3, 3):
+        raise MdlError("fire_cell_state: cell must be [B, 3, 3] float64 with B = %d (got %s %s)" % (B, tuple(cell.shape), cell.dtype))
+
+    def per_structure(v, name, dtype):
+        t = (v.detach() if torch.is_tensor(v) else torch.as_tensor(v)).to(dev)
+        if tuple(t.shape) != (B,):
+            raise MdlError("fire_cell_state: %s must be one value per structure, [%d] (got %s)" % (name, B, tuple(t.shape)))
+        return (t != 0).to(torch.uint8) if dtype == torch.uint8 else t.to(dtype).contiguous()
+
+    free = torch.ones(B, dtype=torch.uint8, device=dev) if cell_free is None else per_structure(cell_free, "cell_free", torch.uint8)
+    if cell_factor is None:
+        factor = (node_ptr[1:] - node_ptr[:-1]).clamp(min=1).to(torch.float64)
+    else:
+        factor = per_structure(cell_factor, "cell_factor", torch.float64)
+        if not bool((factor > 0).all()):
+            raise MdlError("fire_cell_state: cell_factor must be > 0")
+    base = fire_state(B, dt, alpha, dev)
+    return FireCellState(*[getattr(base, k) for k in FireState.__slots__], pos.detach().clone().contiguous(),
+                         torch.eye(3, dtype=torch.float64, device=dev).repeat(B, 1, 1), torch.zeros(B, 3, 3, dtype=torch.float64, device=dev),
+                         cell.detach().clone().contiguous(), free, factor, torch.zeros(B, dtype=torch.float32, device=dev))
+
+
+def fire_cell_step(pos, cell, vel, force, strain_grad, node_ptr, state, fmax, smax, fixed=None, **constants):
+    """One FIRE update (unit masses) over the atoms AND the cell of every structure of a batch, in place, in ONE launch.
+      pos, vel [N, 3] float64 and cell [B, 3, 3] float64 (updated in place: contiguous tensors; vel is the velocity of the scaled
+      rows s), force [N, 3] float32, strain_grad [B, 3, 3] float32 (dE/d eps, NOT divided by the volume: ForceField.evaluate(
+      stress=True, volume_normalised=False)), node_ptr [B + 1] int64, state a FireCellState (updated in place), fmax, smax a number
+      or a [B] float64 tensor each, fixed [N] uint8 / bool or None, constants: any of FIRE_CELL_CONSTANTS (FIRE_CONSTANTS and
+      max_deform in (0, 1)).
+    Coordinates, generalised forces, the convergence rule (max_i |F_i| < fmax AND, where the cell is free, max |dE/d eps| / volume <
+    smax), the trust region (state.done = 2) and the frozen-cell case (the bits of fire_step) are stated in include/mdl_hip.h
+    (mdl_fire_cell_step).  No host synchronisation, no atomics: two calls from the same inputs give the same bits.  Returns state."""
+    unknown = set(constants) - set(FIRE_CELL_CONSTANTS)
+    if unknown:
+        raise MdlError("fire_cell_step: unknown constants %s (known: %s)" % (sorted(unknown), sorted(FIRE_CELL_CONSTANTS)))
+    c = dict(FIRE_CELL_CONSTANTS, **constants)
+    if not isinstance(state, FireCellState):
+        raise MdlError("fire_cell_step: state must be an ops.FireCellState (ops.fire_cell_state)")
+    require_hip(pos, cell, vel, force, strain_grad, node_ptr, fixed, *[getattr(state, k) for k in FireCellState.__slots__])
+    N = pos.shape[0] if pos.dim() == 2 else -1
+    for name, t in (("pos", pos), ("vel", vel), ("state.scaled", state.scaled)):
+        if t.dtype != torch.float64 or tuple(t.shape) != (N, 3) or not t.is_contiguous():
+            raise MdlError("fire_cell_step: %s must be a contiguous [N, 3] float64 tensor (got %s %s)" % (name, tuple(t.shape), t.dtype))
+    if force.dtype != torch.float32 or tuple(force.shape) != (N, 3):
+        raise MdlError("fire_cell_step: force must be [N, 3] float32 with N = %d (got %s %s)" % (N, tuple(force.shape), force.dtype))
+    if node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 1:
+        raise MdlError("fire_cell_step: node_ptr must be [B + 1] int64")
+    B = node_ptr.numel() - 1
+    if cell.dtype != torch.float64 or tuple(cell.shape) != (B, 3, 3) or not cell.is_contiguous():
+        raise MdlError("fire_cell_step: cell must be a contiguous [B, 3, 3] float64 tensor with B = %d (got %s %s)" % (B, tuple(cell.shape), cell.dtype))
+    if strain_grad.dtype != torch.float32 or tuple(strain_grad.shape) != (B, 3, 3):
+        raise MdlError("fire_cell_step: strain_grad must be [B, 3, 3] float32 with B = %d (got %s %s)" % (B, tuple(strain_grad.shape), strain_grad.dtype))
+    for k, dt_, tail in _FIRE_CELL_FIELDS:
+        t = getattr(state, k)
+        if t.dtype != dt_ or tuple(t.shape) != (B,) + tail or not t.is_contiguous():
+            raise MdlError("fire_cell_step: state.%s must be a contiguous %s %s tensor with B = %d (got %s %s)" % (k, list((B,) + tail), dt_, B, tuple(t.shape), t.dtype))
+    bounds = []
+    for name, v in (("fmax", fmax), ("smax", smax)):
+        if torch.is_tensor(v):
+            if v.dtype != torch.float64 or tuple(v.shape) != (B,):
+                raise MdlError("fire_cell_step: %s must be a number or a [B] float64 tensor with B = %d (got %s %s)" % (name, B, tuple(v.shape), v.dtype))
+            require_hip(v)
+            bounds.append(v.contiguous())
+        else:
+            bounds.append(torch.full((B,), float(v), dtype=torch.float64, device=pos.device))
+    if fixed is not None:
+        if fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
+            raise MdlError("fire_cell_step: fixed must be [N] uint8 or bool with N = %d (got %s %s)" % (N, tuple(fixed.shape), fixed.dtype))
+        fixed = fixed.contiguous().view(torch.uint8)
+    if any(t.device != pos.device for t in (cell, vel, force, strain_grad, node_ptr, bounds[0], bounds[1], state.dt, state.scaled)):
+        raise MdlError("fire_cell_step: pos, cell, vel, force, strain_grad, node_ptr, fmax, smax and the state must be on one device")
+    check(lib().mdl_fire_cell_step(ptr(pos), ptr(cell), ptr(state.scaled), ptr(state.deform), ptr(vel), ptr(state.vel_cell), ptr(force.contiguous()),
+                                   ptr(strain_grad.contiguous()), ptr(state.cell0), ptr(fixed), ptr(state.cell_free), ptr(state.cell_factor),
+                                   ptr(node_ptr.contiguous()), N, B, ptr(bounds[0]), ptr(bounds[1]), ptr(state.dt), ptr(state.alpha),
+                                   ptr(state.n_pos), ptr(state.steps), ptr(state.done), ptr(state.fmax_seen), ptr(state.smax_seen),
+                                   int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
+                                   float(c["dt_max"]), float(c["maxstep"]), float(c["max_deform"]), stream()), "mdl_fire_cell_step")
+    return state

@@ -1,0 +1,373 @@
+"""GPU checks of the variable-cell relaxation: the batched FIRE update over atoms and cell of csrc/relax.hip (ops.fire_cell_step)
+against the fp64 restatement that tests/test_relax_cell_host.py owns, its frozen-cell case against ops.fire_step (bit for bit),
+ForceField.set_cell against the existing entry points (bit for bit), and forces.relax_cell against the fp64 reference trajectory
+of the oracle CGCNN at held neighbour lists (bounds: TRAJ_BOUND_POS / TRAJ_BOUND_CELL of the host file)."""
+import numpy as np
+import pytest
+import torch
+
+import test_gpu_forces as tgf
+import test_gpu_relax as tgr
+import test_relax_cell_host as tch
+import test_relax_host as trh
+from test_gpu_forces import DIST_RANGE, DS, dev
+
+pytestmark = pytest.mark.gpu
+
+# the structures of test_gpu_relax with frozen cells (0 .. 8), the same again with free cells (9 .. 17), and three more
+SIZES = tgr.SIZES + tgr.SIZES + [5, 12, 40]
+OFF = len(tgr.SIZES)
+BOTH_CONVERGED, STOPPED, PART_FIXED = 2 * OFF, 2 * OFF + 1, 2 * OFF + 2
+# cell roles of the free half, by structure (FIRE role of test_gpu_relax in brackets)
+GENERIC = OFF + tgr.FREE                 # [uphill-free] deform != I, vel_cell != 0
+FIRST_FREE = OFF + tgr.FIRST             # [first step] the cell's velocity is kept, not mixed
+RESET_FREE = OFF + tgr.RESET             # [P < 0 over atoms and cell] every velocity, the cell's too, starts from zero
+STRESS_DONE = OFF + tgr.CLAMP            # stress below smax, forces not: it moves
+LATCHED_2 = OFF + tgr.LATCHED            # went in with done = 2: stays 2, nothing written
+CELL_ONLY = OFF + tgr.EMPTY              # no atom at all, a stress: the cell alone moves
+FORCES_DONE = OFF + tgr.CONVERGING       # forces below fmax, stress not: it moves
+CELL_CLIPS = OFF + tgr.ACCEL             # the atoms' step is inside maxstep, the cell's rows take it outside
+RIDING = OFF + tgr.ALL_FIXED             # every atom fixed, a stress: the cell moves and the atoms ride with it
+
+
+def _cell_inputs():
+    """seeded inputs that put every branch of the update, FIRE's and the cell's, into one launch"""
+    pos9, vel9, force9, _, st9, fmax9, fixed9 = tgr._fire_inputs()
+    rng = np.random.default_rng(23)
+    node_ptr = np.concatenate([[0], np.cumsum(SIZES)]).astype(np.int64)
+    N, B = int(node_ptr[-1]), len(SIZES)
+    seg = lambda b: slice(node_ptr[b], node_ptr[b + 1])
+    n_extra = N - 2 * len(pos9)
+    force = np.concatenate([force9, force9, (0.3 * rng.normal(size=(n_extra, 3))).astype(np.float32)])
+    vel = np.concatenate([vel9, vel9, 0.7 * (force[2 * len(pos9):].astype(np.float64) + 0.05 * rng.normal(size=(n_extra, 3)))])
+    scaled = np.concatenate([pos9, pos9, rng.uniform(0.0, 10.0, (n_extra, 3))])
+    fixed = np.concatenate([fixed9, fixed9, np.zeros(n_extra, np.uint8)])
+    fixed[seg(PART_FIXED)][::4] = 1
+    cell_free = (np.arange(B) >= OFF).astype(np.uint8)
+    cell0 = np.tile(np.eye(3) * 9.0, (B, 1, 1)) + 0.3 * rng.normal(size=(B, 3, 3))
+    deform = np.tile(np.eye(3), (B, 1, 1))
+    deform[OFF:] += 0.05 * rng.normal(size=(B - OFF, 3, 3))
+    deform[STOPPED] = np.eye(3) * 1.27 + 0.01 * rng.normal(size=(3, 3))
+    cell = np.einsum("bkc,bac->bka", cell0, deform)                       # C = C0 F^T
+    pos = np.concatenate([scaled[seg(b)] @ deform[b].T for b in range(B)])
+    sym = lambda m: 0.5 * (m + m.transpose(0, 2, 1))
+    strain = sym(rng.normal(size=(B, 3, 3))).astype(np.float32)
+    strain[CELL_CLIPS] *= 4.0
+    strain[STOPPED] = (-20.0 * np.eye(3) + sym(rng.normal(size=(1, 3, 3)))[0]).astype(np.float32)
+    cell_factor = np.maximum(1, np.diff(node_ptr)).astype(np.float64)
+    cell_factor[[CELL_CLIPS, STOPPED, RIDING]] = 1.0
+    st = tch.new_cell_state(scaled, cell0, node_ptr, cell_free=cell_free, cell_factor=cell_factor)
+    for k, v in st9.items():
+        st[k] = np.concatenate([v, v, v[[tgr.FREE, tgr.FREE, tgr.FREE]]])
+    st["done"][LATCHED_2] = 2
+    st["smax_seen"][:] = -1.0
+    st["deform"] = deform
+    sign = np.ones(B)
+    sign[RESET_FREE] = -1.0
+    for b in range(OFF, B):                                               # the cell's velocity: along its force, like the atoms'
+        gw = tch.generalised_forces(np.zeros((1, 3)), strain[b].astype(np.float64), deform[b], cell_factor[b])[1]
+        st["vel_cell"][b] = sign[b] * 0.7 * (gw + 0.05 * np.abs(gw).max() * rng.normal(size=(3, 3)))
+    fmax = np.concatenate([fmax9, fmax9, [100.0, 0.05, 0.05]])
+    smax = np.full(B, 1e-5)
+    smax[[STRESS_DONE, BOTH_CONVERGED]] = 100.0
+    return pos, cell, vel, force, strain, node_ptr, st, fmax, smax, fixed
+
+
+def _reference_with_every_role():
+    """the reference's own values: every role is there, and no decision is marginal"""
+    inp = _cell_inputs()
+    pos, cell, vel, force, strain, node_ptr, st, fmax, smax, fixed = inp
+    B, c = len(SIZES), tch.FIRE_CELL_CONSTANTS
+    ref = tch.fire_cell_reference(*inp)
+    rpos, rcell, rvel, rst, diag = ref
+    fire_roles = {tgr.FIRST: "first", tgr.FREE: "uphill-free", tgr.RESET: "reset", tgr.CLAMP: "accelerate", tgr.LATCHED: "latched",
+                  tgr.EMPTY: "converged", tgr.CONVERGING: "converged", tgr.ACCEL: "accelerate", tgr.ALL_FIXED: "converged"}
+    want = dict(fire_roles)
+    want.update({OFF + b: r for b, r in fire_roles.items()})
+    want.update({CELL_ONLY: "first", FORCES_DONE: "uphill-free", RIDING: "uphill-free", BOTH_CONVERGED: "converged", STOPPED: "stopped",
+                 PART_FIXED: "uphill-free"})
+    assert {b: diag[b]["branch"] for b in range(B)} == want
+    assert not st["cell_free"][:OFF].any() and st["cell_free"][OFF:].all()
+    assert np.abs(st["deform"][GENERIC] - np.eye(3)).max() > 0.01 and np.abs(st["vel_cell"][GENERIC]).max() > 0
+    d = diag[FORCES_DONE]
+    assert d["force_ok"] and not d["stress_ok"] and d["fm"] > 0 and rst["steps"][FORCES_DONE] == st["steps"][FORCES_DONE] + 1
+    d = diag[STRESS_DONE]
+    assert d["stress_ok"] and not d["force_ok"] and d["sm"] > 0 and rst["steps"][STRESS_DONE] == st["steps"][STRESS_DONE] + 1
+    assert diag[BOTH_CONVERGED]["force_ok"] and diag[BOTH_CONVERGED]["stress_ok"] and diag[BOTH_CONVERGED]["fm"] > 0 and diag[BOTH_CONVERGED]["sm"] > 0
+    assert diag[CELL_ONLY]["fm"] == 0 and diag[RIDING]["fm"] == 0 and not diag[CELL_ONLY]["stress_ok"] and not diag[RIDING]["stress_ok"]
+    assert diag[CELL_CLIPS]["s_atoms"] < c["maxstep"] * (1 - 1e-3) and diag[CELL_CLIPS]["s"] > c["maxstep"] * (1 + 1e-3)
+    assert rst["done"][STOPPED] == 2 and diag[STOPPED]["dev"] > c["max_deform"] * (1 + 1e-3) and rst["done"][LATCHED_2] == 2
+    assert np.abs(rst["vel_cell"][RESET_FREE] - rst["dt"][RESET_FREE] * tch.generalised_forces(
+        np.zeros((1, 3)), strain[RESET_FREE].astype(np.float64), st["deform"][RESET_FREE], st["cell_factor"][RESET_FREE])[1]).max() < 1e-15
+    moving = [b for b in range(B) if diag[b]["branch"] not in ("converged", "latched", "stopped")]
+    clipped = [b for b in moving if diag[b]["s"] > c["maxstep"]]
+    assert clipped and len(clipped) < len(moving)
+    for b in range(B):
+        d = diag[b]
+        if d["branch"] in ("uphill-free", "accelerate", "reset") or (d["branch"] == "stopped" and st["steps"][b] != 0):
+            assert abs(d["P"]) >= 1e-3 * d["abs_fv"], (b, d)
+        if b in moving or d["branch"] == "stopped":
+            assert abs(d["s"] - c["maxstep"]) >= 1e-3 * c["maxstep"], (b, d)
+            if st["cell_free"][b]:
+                assert abs(d["dev"] - c["max_deform"]) >= 1e-3 * c["max_deform"], (b, d)
+        if not st["done"][b]:
+            if d["fm"] > 0:
+                assert abs(d["fm"] - fmax[b]) >= 1e-3 * fmax[b], (b, d)
+            if st["cell_free"][b] and d["sm"] > 0:
+                assert abs(d["sm"] - smax[b]) >= 1e-3 * smax[b], (b, d)
+    untouched = [b for b in range(B) if diag[b]["branch"] in ("converged", "latched", "stopped")]
+    return inp, ref, moving, untouched
+
+
+STATE_FIELDS = ("dt", "alpha", "n_pos", "steps", "done", "fmax_seen", "scaled", "deform", "vel_cell", "cell0", "cell_free", "cell_factor", "smax_seen")
+
+
+def _to_dev(pos, cell, vel, force, strain, node_ptr, st, fmax, smax, fixed):
+    from matdeeplearn_amd import ops
+    d = dev()
+    t = lambda a: None if a is None else torch.from_numpy(np.array(a)).to(d)
+    assert ops.FireCellState.__slots__ == STATE_FIELDS
+    return t(pos), t(cell), t(vel), t(force), t(strain), t(node_ptr), ops.FireCellState(*[t(st[k]) for k in STATE_FIELDS]), t(fmax), t(smax), t(fixed)
+
+
+def test_fire_cell_step_matches_the_host_reference_in_every_branch():
+    from matdeeplearn_amd import ops
+    inp, (rpos, rcell, rvel, rst, diag), moving, untouched = _reference_with_every_role()
+    pos, cell, vel, force, strain, node_ptr, st, fmax, smax, fixed = inp
+    B = len(SIZES)
+
+    def launch():
+        a = _to_dev(*inp)
+        out = ops.fire_cell_step(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9])
+        assert out is a[6]
+        return a[0], a[1], a[2], a[6]
+
+    dpos, dcell, dvel, state = launch()
+    host = lambda t: t.cpu().numpy()
+    for k in ("n_pos", "steps", "done"):
+        assert np.array_equal(host(getattr(state, k)), rst[k]), (k, getattr(state, k), rst[k])
+    for name, got, ref in (("pos", dpos, rpos), ("cell", dcell, rcell), ("scaled", state.scaled, rst["scaled"]), ("deform", state.deform, rst["deform"]),
+                           ("vel", dvel, rvel), ("vel_cell", state.vel_cell, rst["vel_cell"]), ("dt", state.dt, rst["dt"]),
+                           ("alpha", state.alpha, rst["alpha"])):
+        err = np.abs(host(got) - ref).max()
+        print("%s: max abs err %.3e, scale %.3e (bound 1e-12 of scale)" % (name, err, np.abs(ref).max()))
+        assert err <= 1e-12 * np.abs(ref).max(), name
+    for k in ("fmax_seen", "smax_seen"):
+        seen = host(getattr(state, k))
+        assert (np.abs(seen - rst[k]) <= np.spacing(np.abs(rst[k]))).all(), (k, seen, rst[k])
+    assert (host(state.smax_seen)[OFF:] > 0).all()
+    # what the update must not touch is bitwise what went in: converged, latched and stopped structures as a whole ...
+    for b in untouched:
+        sl = slice(node_ptr[b], node_ptr[b + 1])
+        assert np.array_equal(host(dpos)[sl], pos[sl]) and np.array_equal(host(dvel)[sl], vel[sl]), b
+        assert np.array_equal(host(state.scaled)[sl], st["scaled"][sl]), b
+        for k in ("dt", "alpha", "n_pos", "steps", "deform", "vel_cell"):
+            assert np.array_equal(host(getattr(state, k))[b], st[k][b]), (b, k)
+        assert np.array_equal(host(dcell)[b], cell[b]), b
+    assert [int(state.done[b]) for b in (tgr.LATCHED, LATCHED_2, STOPPED, BOTH_CONVERGED)] == [1, 2, 2, 1]
+    # ... and the cell of every structure whose cell is frozen
+    for b in range(OFF):
+        assert np.array_equal(host(dcell)[b], cell[b]) and np.array_equal(host(state.deform)[b], st["deform"][b])
+        assert np.array_equal(host(state.vel_cell)[b], st["vel_cell"][b])
+    assert torch.equal(state.cell0, _to_dev(*inp)[6].cell0)
+    # fixed atoms of moving structures keep s, lose their velocity and ride with the cell
+    mv = np.zeros(len(pos), bool)
+    for b in moving:
+        mv[node_ptr[b]:node_ptr[b + 1]] = True
+    fx = (fixed != 0) & mv
+    assert fx.any() and np.array_equal(host(state.scaled)[fx], st["scaled"][fx]) and not host(dvel)[fx].any()
+    ride = slice(node_ptr[RIDING], node_ptr[RIDING + 1])
+    assert (host(dpos)[ride] != pos[ride]).any(1).all() and (host(dcell)[RIDING] != cell[RIDING]).any()
+    assert (host(dcell)[CELL_ONLY] != cell[CELL_ONLY]).any()
+    # no atomics: a second launch from the same inputs gives the same bits
+    dpos2, dcell2, dvel2, state2 = launch()
+    assert torch.equal(dpos, dpos2) and torch.equal(dcell, dcell2) and torch.equal(dvel, dvel2)
+    for k in STATE_FIELDS:
+        assert tgr._same(getattr(state, k), getattr(state2, k)), k
+    # without a mask, with scalar bounds and constants of the caller's
+    a = _to_dev(*inp)
+    ops.fire_cell_step(a[0], a[1], a[2], a[3], a[4], a[5], a[6], 0.05, 1e-5, maxstep=0.05, f_dec=0.25, max_deform=0.3)
+    r3 = tch.fire_cell_reference(pos, cell, vel, force, strain, node_ptr, st, 0.05, 1e-5, None, maxstep=0.05, f_dec=0.25, max_deform=0.3)
+    assert np.array_equal(host(a[6].done), r3[3]["done"]) and np.array_equal(host(a[6].steps), r3[3]["steps"])
+    assert np.abs(host(a[0]) - r3[0]).max() <= 1e-12 * np.abs(r3[0]).max() and np.abs(host(a[1]) - r3[1]).max() <= 1e-12 * np.abs(r3[1]).max()
+
+
+def test_fire_cell_step_with_frozen_cells_is_fire_step_to_the_bit():
+    from matdeeplearn_amd import ops
+    pos, cell, vel, force, strain, node_ptr, st, cst, fmax, fixed = tch.frozen_inputs()
+    dpos, dvel, dforce, dptr, state, dfmax, dfixed = tgr._to_dev(pos, vel, force, node_ptr, st, fmax, fixed)
+    ops.fire_step(dpos, dvel, dforce, dptr, state, dfmax, dfixed)
+    smax = np.zeros(len(node_ptr) - 1)
+    cpos, ccell, cvel, cforce, cstrain, cptr, cstate, cfmax, csmax, cfixed = _to_dev(pos, cell, vel, force, strain, node_ptr, cst, fmax, smax, fixed)
+    before = cstate.clone()
+    ops.fire_cell_step(cpos, ccell, cvel, cforce, cstrain, cptr, cstate, cfmax, csmax, cfixed)
+    assert torch.equal(cpos, dpos) and torch.equal(cvel, dvel)
+    for k in ops.FireState.__slots__:
+        assert torch.equal(getattr(cstate, k), getattr(state, k)), k
+    assert (state.steps.cpu().numpy() != st["steps"]).sum() >= 5                    # most of them moved
+    assert torch.equal(ccell, torch.from_numpy(cell).to(dev()))
+    for k in ("deform", "vel_cell", "cell0"):
+        assert torch.equal(getattr(cstate, k), getattr(before, k)), k
+    assert torch.equal(cstate.scaled, cpos)
+    # and without a mask
+    a = tgr._to_dev(pos, vel, force, node_ptr, st, fmax, fixed)
+    ops.fire_step(a[0], a[1], a[2], a[3], a[4], 0.05)
+    b = _to_dev(pos, cell, vel, force, strain, node_ptr, cst, fmax, smax, None)
+    ops.fire_cell_step(b[0], b[1], b[2], b[3], b[4], b[5], b[6], 0.05, 0.0)
+    assert torch.equal(b[0], a[0]) and torch.equal(b[2], a[1]) and torch.equal(b[6].dt, a[4].dt) and torch.equal(b[6].done, a[4].done)
+
+
+# ---------------------------------------------------------------------------------------------
+# 3. ForceField.set_cell
+# ---------------------------------------------------------------------------------------------
+def _structs_of(structs, pos, cell, node_ptr):
+    return [dict(s, positions=pos[a:b], cell=cell[k]) for k, (s, a, b) in enumerate(zip(structs, node_ptr[:-1], node_ptr[1:]))]
+
+
+@pytest.mark.parametrize("kind", ["cgcnn", "schnet"])
+def test_set_cell_scales_the_atoms_and_evaluates_like_the_existing_path(kind):
+    from matdeeplearn_amd import forces, ops
+    model = tgr._model(kind)
+    structs = tgf._bulk_structures(8, seed=2, lo=4, hi=30)
+    p = tgf._pack(structs)
+    rng = np.random.default_rng(9)
+    new = np.einsum("bkc,bac->bka", p["cell"], np.eye(3) + 0.03 * rng.normal(size=(8, 3, 3)))
+    with ops.deterministic():
+        ff = forces.ForceField(model, structs, DIST_RANGE)
+        src0 = ff.edges[0].clone()
+        ff.set_cell(new)                                               # the cell alone: positions keep their bits
+        assert torch.equal(ff.positions.cpu(), torch.from_numpy(p["pos"])) and torch.equal(ff.cell.cpu(), torch.from_numpy(new))
+        ff.set_cell(torch.from_numpy(p["cell"]).to(dev()))
+        ff.set_cell(new, scale_atoms=True)
+        assert torch.equal(ff.edges[0], src0)                          # the lists are not touched
+        pos = ff.positions.cpu().numpy()
+        frac_old = np.concatenate([p["pos"][a:b] @ np.linalg.inv(p["cell"][k]) for k, (a, b) in enumerate(zip(p["node_ptr"][:-1], p["node_ptr"][1:]))])
+        frac_new = np.concatenate([pos[a:b] @ np.linalg.inv(new[k]) for k, (a, b) in enumerate(zip(p["node_ptr"][:-1], p["node_ptr"][1:]))])
+        assert np.abs(frac_new - frac_old).max() <= 1e-13 and np.abs(pos - p["pos"]).max() > 1e-3
+        ff.rebuild()
+        got = ff.evaluate(stress=True)
+        ref = forces.energy_forces_stress(model, _structs_of(structs, pos, ff.cell.cpu().numpy(), p["node_ptr"]), DIST_RANGE)
+        first = forces.energy_forces_stress(model, structs, DIST_RANGE)
+    for a, b in zip(got, ref[:3]):
+        assert tgr._same(a, b)
+    assert not torch.equal(got[0], first[0]) and not torch.equal(got[2], first[2])
+    for bad in (np.zeros((3, 3)), np.zeros((7, 3, 3)), np.zeros((8, 9))):
+        with pytest.raises(ops.MdlError, match="set_cell"):
+            ff.set_cell(bad)
+    # a structure without a cell keeps its atoms where they are
+    mixed = tgf._mixed_structures()[:4]
+    fm = forces.ForceField(model, mixed, DIST_RANGE)
+    pm = tgf._pack(mixed)
+    fm.set_cell(pm["cell"] * 1.02, scale_atoms=True)
+    got_pos = fm.positions.cpu().numpy()
+    mol = slice(pm["node_ptr"][3], pm["node_ptr"][4])
+    assert np.array_equal(got_pos[mol], pm["pos"][mol]) and np.abs(got_pos[:pm["node_ptr"][3]] - 1.02 * pm["pos"][:pm["node_ptr"][3]]).max() < 1e-12
+
+
+# ---------------------------------------------------------------------------------------------
+# 4. relax_cell against the fp64 reference trajectory
+# ---------------------------------------------------------------------------------------------
+def test_relax_cell_follows_the_fp64_reference_trajectory_at_held_lists():
+    from matdeeplearn_amd import forces, models, ops
+    case = trh.cgcnn_case()
+    ref_pos, ref_cell, ref_e, _, _ = tch.cgcnn_cell_reference()
+    model = models.CGCNN(DS(), dim1=64, dim2=64, gc_count=2, post_fc_count=1)
+    model.load_state_dict(case.state_dict)
+    model.to(dev()).eval()
+    B = len(case.structs)
+    with ops.deterministic():
+        e0 = forces.energy_and_forces(model, case.structs, DIST_RANGE)[0]
+        res = forces.relax_cell(model, case.structs, DIST_RANGE, rebuild_every=0, **tch.RELAX_CELL_ARGS)
+        again = forces.relax_cell(model, case.structs, DIST_RANGE, rebuild_every=0, **tch.RELAX_CELL_ARGS)
+    assert res.positions.dtype == torch.float64 and res.cell.dtype == torch.float64 and res.forces.dtype == torch.float32
+    assert res.stress.dtype == torch.float32 and tuple(res.stress.shape) == (B, 3, 3) and res.smax.dtype == torch.float32
+    assert res.converged.dtype == torch.bool and res.steps.dtype == torch.int32 and res.status.dtype == torch.int32
+    dev_pos = np.sqrt(((res.positions.cpu().numpy() - ref_pos) ** 2).sum(1)).max()
+    dev_cell = np.sqrt(((res.cell.cpu().numpy() - ref_cell) ** 2).sum(2)).max()
+    print("largest distance from the reference trajectory: atoms %.3e A (TRAJ_BOUND_POS %.1e), lattice vectors %.3e A (TRAJ_BOUND_CELL %.1e)"
+          % (dev_pos, tch.TRAJ_BOUND_POS, dev_cell, tch.TRAJ_BOUND_CELL))
+    print("energies: start", e0.cpu().numpy(), "end", res.energy.cpu().numpy(), "reference end", ref_e[-1])
+    assert dev_pos <= tch.TRAJ_BOUND_POS and dev_cell <= tch.TRAJ_BOUND_CELL
+    assert (res.energy < e0).all()
+    assert (res.steps == tch.RELAX_CELL_ARGS["steps"]).all() and not res.converged.any() and not res.status.any()
+    vol = torch.linalg.det(res.cell.cpu())
+    sm = res.stress.double().cpu().abs().flatten(1).max(1).values
+    assert torch.allclose(res.smax.double().cpu(), sm, rtol=1e-5, atol=0) and (vol > 0).all()
+    for a, b in zip(res, again):
+        assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------------------------------------
+# 5. a mixed batch on rebuilt lists; refusals
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["cgcnn", "schnet"])
+def test_relax_cell_mixed_batch_freezes_rebuilds_and_leaves_slabs_and_molecules_to_relax(kind):
+    """rebuild_every=1, 10 steps at dt = 3 (seeded, untrained models, as in test_gpu_relax).  8 bulk structures, then 2 slabs and 2
+    molecules.  Every second structure gets fmax and smax above its first values and must come back bit for bit; the others move."""
+    from matdeeplearn_amd import forces, ops
+    model = tgr._model(kind)
+    mixed = tgf._mixed_structures()
+    structs = tgf._bulk_structures(8, seed=4, lo=4, hi=24) + [mixed[2], mixed[6], mixed[3], mixed[7]]
+    p = tgf._pack(structs)
+    node_ptr, B = p["node_ptr"], 12
+    bulk = np.arange(B) < 8
+    args = dict(steps=10, rebuild_every=1, dt=3.0, dt_max=30.0)
+    with ops.deterministic():
+        e0, f0, s0, _ = forces.energy_forces_stress(model, structs, DIST_RANGE)
+        f0n = f0.double().cpu().numpy()
+        fm0 = np.array([np.sqrt((f0n[a:b] ** 2).sum(1)).max() for a, b in zip(node_ptr[:-1], node_ptr[1:])])
+        sm0 = np.nan_to_num(s0.double().abs().flatten(1).max(1).values.cpu().numpy(), nan=1.0)
+        assert (fm0 > 0).all() and (sm0[:8] > 0).all() and torch.isnan(s0[8:]).all() and not torch.isnan(s0[:8]).any()
+        still = np.arange(B) % 2 == 0
+        fmax, smax = np.where(still, 2.0 * fm0, 0.0), np.where(still, 2.0 * sm0, 0.0)
+        res = forces.relax_cell(model, structs, DIST_RANGE, fmax=fmax, smax=smax, **args)
+        fixed_cell = forces.relax(model, structs, DIST_RANGE, fmax=fmax, **args)
+    pos, cell = res.positions.cpu().numpy(), res.cell.cpu().numpy()
+    for b in range(B):
+        sl = slice(node_ptr[b], node_ptr[b + 1])
+        if still[b]:                                            # frozen from the first step: the input bits
+            assert np.array_equal(pos[sl], p["pos"][sl]) and np.array_equal(cell[b], p["cell"][b]), b
+            assert int(res.steps[b]) == 0 and bool(res.converged[b]) and int(res.status[b]) == 1, b
+        else:
+            assert (pos[sl] != p["pos"][sl]).any(1).all(), b
+            assert int(res.steps[b]) == 10 and not bool(res.converged[b]) and int(res.status[b]) == 0, b
+            assert (cell[b] != p["cell"][b]).any() == bool(bulk[b]), b
+        if not bulk[b]:                                         # no cell to move: relax, to the bit, and the cell as it went in
+            assert np.array_equal(cell[b], p["cell"][b]) and np.array_equal(pos[sl], fixed_cell.positions.cpu().numpy()[sl]), b
+    print("energies: start", e0.cpu().numpy(), "end", res.energy.cpu().numpy())
+    assert (res.energy[~torch.from_numpy(still)] < e0[~torch.from_numpy(still)]).all()
+    # the returned energy, forces and stress belong to the returned positions and cell on REBUILT lists: the existing path gives them back
+    with ops.deterministic():
+        e1, f1, s1, _ = forces.energy_forces_stress(model, _structs_of(structs, pos, cell, node_ptr), DIST_RANGE)
+    assert tgr._same(res.energy, e1) and tgr._same(res.forces, f1) and tgr._same(res.stress, s1)
+    assert torch.isnan(res.smax[8:]).all() and not torch.isnan(res.smax[:8]).any()
+
+
+def test_relax_cell_refuses_what_it_cannot_do():
+    from matdeeplearn_amd import forces, models, ops
+    structs = tgf._bulk_structures(2, seed=4, lo=4, hi=8)
+    model = tgr._model("cgcnn")
+    model.train()
+    with pytest.raises(ops.MdlError, match="eval"):
+        forces.relax_cell(model, structs, DIST_RANGE, steps=1)
+    model.eval()
+    gcn = models.GCN(DS(), dim1=64, dim2=64, gc_count=1, post_fc_count=1).to(dev()).eval()
+    with pytest.raises(ops.MdlError, match="forces are implemented for CGCNN"):
+        forces.relax_cell(gcn, structs, DIST_RANGE, steps=1)
+    for kw in (dict(smax=[1e-3] * 3), dict(fmax=np.zeros((2, 2))), dict(cell_free=[1, 0, 1]), dict(cell_factor=[1.0]), dict(cell_factor=[1.0, -2.0]),
+               dict(max_deform=0.0), dict(max_deform=1.0), dict(max_deform=float("nan")), dict(fixed=np.zeros(3)), dict(steps=-1)):
+        with pytest.raises(ops.MdlError):
+            forces.relax_cell(model, structs, DIST_RANGE, **dict(dict(steps=1), **kw))
+    # the library refuses max_deform outside (0, 1) too
+    p = tgf._pack(structs)
+    t = lambda a: torch.from_numpy(a).to(dev())
+    pos, cell, ptr = t(p["pos"]), t(p["cell"]), t(p["node_ptr"])
+    state = ops.fire_cell_state(pos, cell, ptr)
+    for bad in (0.0, 1.0, -0.5, 1.5):
+        with pytest.raises(ops.MdlError, match="max_deform"):
+            ops.fire_cell_step(pos, cell, torch.zeros_like(pos), torch.zeros(pos.shape[0], 3, device=dev()), torch.zeros(2, 3, 3, device=dev()), ptr,
+                               state, 0.05, 1e-3, max_deform=bad)
+    with pytest.raises(ops.MdlError, match="unknown constants"):
+        ops.fire_cell_step(pos, cell, torch.zeros_like(pos), torch.zeros(pos.shape[0], 3, device=dev()), torch.zeros(2, 3, 3, device=dev()), ptr,
+                           state, 0.05, 1e-3, max_deformation=0.2)
+    assert torch.equal(pos, t(p["pos"])) and torch.equal(cell, t(p["cell"])) and not state.steps.any()
