@@ -725,7 +725,9 @@ int mdl_fire_step(double* pos, double* vel, const float* force, const uint8_t* f
  *      as zero), cell = C0 F'^T, velocities and state as mdl_fire_step, steps += 1.  0 < max_deform < 1 bounds the smallest
  *      singular value of every F the caller can see from below by 1 - max_deform: no accepted cell is degenerate.
  *   cell_free[b] == 0: the cell rows contribute nothing, F is taken as I; pos, vel and the state get the bits of mdl_fire_step
- *      on the same inputs, scaled gets the bits of pos, and cell, deform and vel_cell of b are not written.
+ *      on the same inputs (both functions launch one kernel body, written with contraction off and explicit fmas; the frozen
+ *      path of this one is all there is of the other), scaled gets the bits of pos, and cell, deform and vel_cell of b are not
+ *      written.
  * The 3x3 algebra is done by every lane from the same values; lane 0 alone reads and writes what is per structure.  Sums as in
  * mdl_fire_step: no atomics, bitwise repeatable.  Argument checks of mdl_fire_step plus 0 < max_deform < 1. */
 int mdl_fire_cell_step(double* pos, double* cell, double* scaled, double* deform, double* vel, double* vel_cell, const float* force,

@@ -1,7 +1,9 @@
 // relax.hip — one FIRE update (Bitzek et al., PRL 97, 170201 (2006); unit masses) of a BATCH of structures in one launch.
 // No reference counterpart: the reference has no force path and no optimiser of atomic positions.
 //
-//   mdl_fire_step   one workgroup of 256 lanes per structure, looping over the structure's atoms; all arithmetic fp64.
+// ONE kernel body, fire_kernel<CELL>, instantiated twice:
+//   mdl_fire_step        fire_kernel<false>: one workgroup of 256 lanes per structure, looping over the structure's atoms; all
+//                   arithmetic fp64.
 //                   pass 1: |f|^2, f.v, |v|^2 and max_i |f_i|^2 of the structure (forces of fixed atoms count as zero) -> the
 //                           convergence latch and the branch of the velocity mixing, decided by every lane from the same
 //                           four numbers;
@@ -12,11 +14,14 @@
 //                   every run.  Lane 0 alone reads and writes the per-structure state, so no lane can see a half-updated one.
 //                   A converged structure (latched before, or max_i |f_i| < fmax, or no force on a free atom) gets done = 1 and
 //                   fmax_seen; nothing else of it is written.
-//   mdl_fire_cell_step   the same update over the atoms and the cell: the rows s_i (pos_i = F s_i) and the three rows of W = cf F,
-//                   F the deformation gradient of the cell the relaxation started from.  Same workgroup, same sums; the 3x3
-//                   algebra (F^-1 through the adjugate, S F^-T, det cell) is done by every lane from the same nine numbers.  A
-//                   structure whose cell is frozen takes the code of mdl_fire_step and gets its bits; a step whose F' leaves
-//                   |F' - I| <= max_deform is refused as a whole (done = 2) before anything of it is written.
+//   mdl_fire_cell_step   fire_kernel<true>: the same update over the atoms and the cell: the rows s_i (pos_i = F s_i) and the three
+//                   rows of W = cf F, F the deformation gradient of the cell the relaxation started from.  Same workgroup, same
+//                   sums; the 3x3 algebra (F^-1 through the adjugate, S F^-T, det cell) is done by every lane from the same nine
+//                   numbers.  A step whose F' leaves |F' - I| <= max_deform is refused as a whole (done = 2) before anything of
+//                   it is written.
+// The bits: contraction is off in the kernel and every fused multiply-add is written out, so the source states the arithmetic
+// (fp64 sqrt and / are correctly rounded, no fast-math flag is in the build).  A structure whose cell is frozen runs, in
+// fire_kernel<true>, the statements that are all of fire_kernel<false>: it gets the bits of mdl_fire_step because it is that code.
 #include "mdl_common.h"
 
 namespace mdl {
@@ -55,121 +60,23 @@ struct FireConst {
     double f_inc, f_dec, alpha_start, f_alpha, dt_max, maxstep;
 };
 
-__global__ __launch_bounds__(FIRE_THREADS) void fire_step_kernel(double* __restrict__ pos, double* __restrict__ vel,
-                                                                 const float* __restrict__ force, const uint8_t* __restrict__ fixed,
-                                                                 const int64_t* __restrict__ node_ptr, int64_t N,
-                                                                 const double* __restrict__ fmax, double* dt_io, double* alpha_io,
-                                                                 int32_t* n_pos_io, int32_t* steps_io, int32_t* done_io,
-                                                                 float* __restrict__ fmax_seen, FireConst c) {
-    __shared__ double red1[FIRE_WAVES][4];
-    __shared__ double red2[FIRE_WAVES][1];
-    __shared__ double st_d[3];
-    __shared__ int32_t st_i[3];
-    const int64_t b = blockIdx.x;
-    int64_t n0 = node_ptr[b], n1 = node_ptr[b + 1];
-    n0 = n0 < 0 ? 0 : (n0 > N ? N : n0);
-    n1 = n1 < n0 ? n0 : (n1 > N ? N : n1);
-    if (threadIdx.x == 0) {
-        st_d[0] = dt_io[b];
-        st_d[1] = alpha_io[b];
-        st_d[2] = fmax[b];
-        st_i[0] = n_pos_io[b];
-        st_i[1] = steps_io[b];
-        st_i[2] = done_io[b];
-    }
-
-    // pass 1: acc = (|f|^2, f.v, |v|^2 | max_i |f_i|^2); a fixed atom has f = 0 and v = 0
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t i = n0 + threadIdx.x; i < n1; i += FIRE_THREADS) {
-        if (fixed && fixed[i]) continue;
-        const double fx = (double)force[i * 3 + 0], fy = (double)force[i * 3 + 1], fz = (double)force[i * 3 + 2];
-        const double vx = vel[i * 3 + 0], vy = vel[i * 3 + 1], vz = vel[i * 3 + 2];
-        const double f2 = fx * fx + fy * fy + fz * fz;
-        acc[0] += f2;
-        acc[1] += fx * vx + fy * vy + fz * vz;
-        acc[2] += vx * vx + vy * vy + vz * vz;
-        acc[3] = f2 > acc[3] ? f2 : acc[3];
-    }
-    block_reduce<4, 3>(acc, red1);                             // (its barrier also publishes st_d / st_i)
-    const double ff = acc[0], P = acc[1], vv = acc[2], fm = sqrt(acc[3]);
-    double dt = st_d[0], alpha = st_d[1];
-    int32_t n_pos = st_i[0];
-    const int32_t steps = st_i[1];
-    const bool converged = st_i[2] != 0 || fm < st_d[2] || !(fm > 0.0);
-    if (threadIdx.x == 0) fmax_seen[b] = (float)fm;
-    if (converged) {                                           // uniform over the workgroup
-        if (threadIdx.x == 0) done_io[b] = 1;
-        return;
-    }
-
-    // velocity mixing: v <- c_v v + c_f f
-    double c_v = 1.0, c_f = 0.0;
-    if (steps != 0) {
-        if (P > 0.0) {
-            c_v = 1.0 - alpha;
-            c_f = alpha * (sqrt(vv) / sqrt(ff));
-            if (n_pos > c.n_min) {
-                const double grown = dt * c.f_inc;
-                dt = grown < c.dt_max ? grown : c.dt_max;
-                alpha = alpha * c.f_alpha;
-            }
-            n_pos += 1;
-        } else {
-            c_v = 0.0;
-            alpha = c.alpha_start;
-            dt = dt * c.f_dec;
-            n_pos = 0;
-        }
-    }
-
-    // pass 2: v <- (c_v v + c_f f) + dt f;  |dt v|^2
-    double s2[1] = {0.0};
-    for (int64_t i = n0 + threadIdx.x; i < n1; i += FIRE_THREADS) {
-        double vx = 0.0, vy = 0.0, vz = 0.0;
-        if (!(fixed && fixed[i])) {
-            const double fx = (double)force[i * 3 + 0], fy = (double)force[i * 3 + 1], fz = (double)force[i * 3 + 2];
-            vx = (c_v * vel[i * 3 + 0] + c_f * fx) + dt * fx;
-            vy = (c_v * vel[i * 3 + 1] + c_f * fy) + dt * fy;
-            vz = (c_v * vel[i * 3 + 2] + c_f * fz) + dt * fz;
-        }
-        vel[i * 3 + 0] = vx;
-        vel[i * 3 + 1] = vy;
-        vel[i * 3 + 2] = vz;
-        const double dx = dt * vx, dy = dt * vy, dz = dt * vz;
-        s2[0] += dx * dx + dy * dy + dz * dz;
-    }
-    block_reduce<1, 1>(s2, red2);
-    const double s = sqrt(s2[0]);
-    const double clip = s > c.maxstep ? c.maxstep / s : 1.0;
-
-    // pass 3: pos += dt v (clipped); every lane re-reads the velocities it wrote itself
-    for (int64_t i = n0 + threadIdx.x; i < n1; i += FIRE_THREADS) {
-        if (fixed && fixed[i]) continue;
-        pos[i * 3 + 0] += (dt * vel[i * 3 + 0]) * clip;
-        pos[i * 3 + 1] += (dt * vel[i * 3 + 1]) * clip;
-        pos[i * 3 + 2] += (dt * vel[i * 3 + 2]) * clip;
-    }
-    if (threadIdx.x == 0) {
-        dt_io[b] = dt;
-        alpha_io[b] = alpha;
-        n_pos_io[b] = n_pos;
-        steps_io[b] = steps + 1;
-    }
-}
-
-// ---- the same update over atoms and cell (include/mdl_hip.h, mdl_fire_cell_step) ----------------------------------------------
-struct FireCellArgs {
-    double *pos, *cell, *scaled, *deform, *vel, *vel_cell;
-    const float *force, *strain_grad;
-    const double* cell0;
-    const uint8_t *fixed, *cell_free;
-    const double* cell_factor;
+// the operands of both entry points; what only the cell's degrees of freedom need is null for mdl_fire_step and never read there
+struct FireArgs {
+    double *pos, *vel;
+    const float* force;
+    const uint8_t* fixed;
     const int64_t* node_ptr;
     int64_t N;
-    const double *fmax, *smax;
+    const double* fmax;
     double *dt, *alpha;
     int32_t *n_pos, *steps, *done;
-    float *fmax_seen, *smax_seen;
+    float* fmax_seen;
+    double *cell, *scaled, *deform, *vel_cell;
+    const float* strain_grad;
+    const double* cell0;
+    const uint8_t* cell_free;
+    const double *cell_factor, *smax;
+    float* smax_seen;
 };
 
 // row-major 3x3: the adjugate (inverse times determinant) and the determinant
@@ -187,53 +94,60 @@ __device__ __forceinline__ double adjugate3(const double* m, double* adj) {
     return m[0] * adj[0] + m[1] * adj[3] + m[2] * adj[6];
 }
 
-// The atoms' passes are those of fire_step_kernel with the generalised force g = F^T f in the place of f (g = f, the same bits,
-// where the cell is frozen); the three rows of W enter every sum behind the workgroup's reduction, from values every lane holds,
-// and not at all where the cell is frozen.  Nothing of a structure is written before the trust region has accepted its new F:
-// the velocities of a structure with a free cell are formed twice (pass 2 for the step's length, pass 3 to be stored).
-// The bits of fire_step_kernel: its products and sums are written out here as the compiler fuses them there (contraction is off
-// in this kernel, every fma below is one of fire_step_kernel's) — x^2 + y^2 + z^2 as fma(z, z, fma(x, x, y y)), the mixing as
-// fma(dt, g, fma(c_f, g, c_v v)), the step as fma(clip, dt v, pos).
-__global__ __launch_bounds__(FIRE_THREADS) void fire_cell_step_kernel(FireCellArgs a, FireConst c, double max_deform) {
+// CELL = false: the atoms alone (include/mdl_hip.h, mdl_fire_step); free_cell is false at compile time, and no cell matrix, no
+// `scaled` row and no cell pointer is touched.
+// CELL = true: atoms and cell (mdl_fire_cell_step).  The atoms' passes run with the generalised force g = F^T f in the place of f
+// (g = f where the cell is frozen); the three rows of W enter every sum behind the workgroup's reduction, from values every lane
+// holds, and not at all where the cell is frozen.  Nothing of a structure is written before the trust region has accepted its new
+// F: the velocities of a structure with a free cell are formed twice (pass 2 for the step's length, pass 3 to be stored).
+// Every fma is explicit: x^2 + y^2 + z^2 is fma(z, z, fma(x, x, y y)), the mixing fma(dt, g, fma(c_f, g, c_v v)), the step
+// fma(clip, dt v, pos); the F-transforms and the cell's rows are plain products and sums.
+template <bool CELL>
+__global__ __launch_bounds__(FIRE_THREADS) void fire_kernel(FireArgs a, FireConst c, double max_deform) {
 #pragma clang fp contract(off)
     __shared__ double red1[FIRE_WAVES][4];
     __shared__ double red2[FIRE_WAVES][1];
     __shared__ double st_d[5];
     __shared__ int32_t st_i[4];
-    __shared__ double m_F[9], m_S[9], m_V[9], m_C[9], m_C0[9];
+    __shared__ double m_F[9], m_S[9], m_V[9], m_C[9], m_C0[9];     // CELL only
     const int64_t b = blockIdx.x;
     int64_t n0 = a.node_ptr[b], n1 = a.node_ptr[b + 1];
     n0 = n0 < 0 ? 0 : (n0 > a.N ? a.N : n0);
     n1 = n1 < n0 ? n0 : (n1 > a.N ? a.N : n1);
     if (threadIdx.x == 0) {
-        const bool fr = a.cell_free[b] != 0;
         st_d[0] = a.dt[b];
         st_d[1] = a.alpha[b];
         st_d[2] = a.fmax[b];
-        st_d[3] = a.smax[b];
-        st_d[4] = a.cell_factor[b];
         st_i[0] = a.n_pos[b];
         st_i[1] = a.steps[b];
         st_i[2] = a.done[b];
-        st_i[3] = fr ? 1 : 0;
-        for (int k = 0; k < 9; ++k) {
-            m_S[k] = (double)a.strain_grad[b * 9 + k];
-            m_C[k] = a.cell[b * 9 + k];
-            m_F[k] = fr ? a.deform[b * 9 + k] : (k % 4 == 0 ? 1.0 : 0.0);
-            m_V[k] = fr ? a.vel_cell[b * 9 + k] : 0.0;
-            m_C0[k] = fr ? a.cell0[b * 9 + k] : 0.0;
+        if constexpr (CELL) {
+            const bool fr = a.cell_free[b] != 0;
+            st_d[3] = a.smax[b];
+            st_d[4] = a.cell_factor[b];
+            st_i[3] = fr ? 1 : 0;
+            for (int k = 0; k < 9; ++k) {
+                m_S[k] = (double)a.strain_grad[b * 9 + k];
+                m_C[k] = a.cell[b * 9 + k];
+                m_F[k] = fr ? a.deform[b * 9 + k] : (k % 4 == 0 ? 1.0 : 0.0);
+                m_V[k] = fr ? a.vel_cell[b * 9 + k] : 0.0;
+                m_C0[k] = fr ? a.cell0[b * 9 + k] : 0.0;
+            }
         }
     }
-    __syncthreads();
-    const bool free_cell = st_i[3] != 0;
+    bool free_cell = false;
+    double F[9], S[9], gW[9], V[9], Vn[9], Fn[9];                  // CELL only
+    if constexpr (CELL) {
+        __syncthreads();                                           // free_cell and F are needed in pass 1
+        free_cell = st_i[3] != 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) F[k] = m_F[k];
+    }
     const uint8_t* fixed = a.fixed;
     const float* force = a.force;
     double* vel = a.vel;
-    double F[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) F[k] = m_F[k];
 
-    // pass 1: acc = (|g|^2, g.v, |v|^2 | max_i |f_i|^2) over the atoms
+    // pass 1: acc = (|g|^2, g.v, |v|^2 | max_i |f_i|^2) over the atoms; a fixed atom has f = 0 and v = 0
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t i = n0 + threadIdx.x; i < n1; i += FIRE_THREADS) {
         if (fixed && fixed[i]) continue;
@@ -252,57 +166,61 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_cell_step_kernel(FireCellAr
         acc[2] += __builtin_fma(vz, vz, __builtin_fma(vx, vx, vy * vy));
         acc[3] = f2 > acc[3] ? f2 : acc[3];
     }
-    block_reduce<4, 3>(acc, red1);
+    block_reduce<4, 3>(acc, red1);                             // (its barrier also publishes st_d / st_i)
 
-    // the cell's rows: g_W = -(1 / cf) S F^-T, and the stress criterion sm = max |S| / |det cell|
-    double S[9], gW[9], V[9];
-    double max_s = 0.0;
+    bool stress_ok = true;
+    double cf = 0.0;
+    if constexpr (CELL) {
+        // the cell's rows: g_W = -(1 / cf) S F^-T, and the stress criterion sm = max |S| / |det cell|
+        double max_s = 0.0;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        S[k] = m_S[k];
-        V[k] = m_V[k];
-        gW[k] = 0.0;
-        const double as = fabs(S[k]);
-        max_s = as > max_s || as != as ? as : max_s;           // a NaN stays
-    }
-    double adj[9], C[9];
+        for (int k = 0; k < 9; ++k) {
+            S[k] = m_S[k];
+            V[k] = m_V[k];
+            gW[k] = 0.0;
+            const double as = fabs(S[k]);
+            max_s = as > max_s || as != as ? as : max_s;       // a NaN stays
+        }
+        double adj[9], C[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) C[k] = m_C[k];
-    const double det_c = adjugate3(C, adj);
-    const double sm = det_c != 0.0 ? max_s / fabs(det_c) : __longlong_as_double(0x7ff8000000000000ll);
-    const double cf = st_d[4];
-    if (free_cell) {
-        const double det_f = adjugate3(F, adj);
-        const double scale = -(1.0 / cf);
-        double gg = 0.0, gv = 0.0, vv_c = 0.0;
+        for (int k = 0; k < 9; ++k) C[k] = m_C[k];
+        const double det_c = adjugate3(C, adj);
+        const double sm = det_c != 0.0 ? max_s / fabs(det_c) : __longlong_as_double(0x7ff8000000000000ll);
+        cf = st_d[4];
+        if (free_cell) {
+            const double det_f = adjugate3(F, adj);
+            const double scale = -(1.0 / cf);
+            double gg = 0.0, gv = 0.0, vv_c = 0.0;
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
+            for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const double t = S[r * 3 + 0] * (adj[q * 3 + 0] / det_f) + S[r * 3 + 1] * (adj[q * 3 + 1] / det_f) +
-                                 S[r * 3 + 2] * (adj[q * 3 + 2] / det_f);
-                const double g = scale * t;
-                gW[r * 3 + q] = g;
-                gg += g * g;
-                gv += g * V[r * 3 + q];
-                vv_c += V[r * 3 + q] * V[r * 3 + q];
-            }
-        acc[0] += gg;
-        acc[1] += gv;
-        acc[2] += vv_c;
+                for (int q = 0; q < 3; ++q) {
+                    const double t = S[r * 3 + 0] * (adj[q * 3 + 0] / det_f) + S[r * 3 + 1] * (adj[q * 3 + 1] / det_f) +
+                                     S[r * 3 + 2] * (adj[q * 3 + 2] / det_f);
+                    const double g = scale * t;
+                    gW[r * 3 + q] = g;
+                    gg += g * g;
+                    gv += g * V[r * 3 + q];
+                    vv_c += V[r * 3 + q] * V[r * 3 + q];
+                }
+            acc[0] += gg;
+            acc[1] += gv;
+            acc[2] += vv_c;
+        }
+        stress_ok = !free_cell || sm < st_d[3] || !(sm > 0.0);
+        if (threadIdx.x == 0) a.smax_seen[b] = (float)sm;
     }
     const double ff = acc[0], P = acc[1], vv = acc[2], fm = sqrt(acc[3]);
     double dt = st_d[0], alpha = st_d[1];
     int32_t n_pos = st_i[0];
     const int32_t steps = st_i[1];
+    const bool latched = st_i[2] != 0;
     const bool force_ok = fm < st_d[2] || !(fm > 0.0);
-    const bool stress_ok = !free_cell || sm < st_d[3] || !(sm > 0.0);
-    if (threadIdx.x == 0) {
-        a.fmax_seen[b] = (float)fm;
-        a.smax_seen[b] = (float)sm;
-    }
-    if (st_i[2] != 0) return;                                  // latched (1 or 2): the code stays.  Uniform over the workgroup
-    if (force_ok && stress_ok) {
+    if (threadIdx.x == 0) a.fmax_seen[b] = (float)fm;
+    // every return below is uniform over the workgroup
+    if constexpr (CELL)
+        if (latched) return;                                   // the code (1 converged, 2 trust region) stays; without a cell it becomes 1
+    if (latched || (force_ok && stress_ok)) {
         if (threadIdx.x == 0) a.done[b] = 1;
         return;
     }
@@ -352,33 +270,40 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_cell_step_kernel(FireCellAr
         s2[0] += __builtin_fma(dz, dz, __builtin_fma(dx, dx, dy * dy));
     }
     block_reduce<1, 1>(s2, red2);
-    double Vn[9], Fn[9];
-    if (free_cell) {
-        double s2_c = 0.0;
+    if constexpr (CELL)
+        if (free_cell) {
+            double s2_c = 0.0;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            Vn[k] = (c_v * V[k] + c_f * gW[k]) + dt * gW[k];
-            const double d = dt * Vn[k];
-            s2_c += d * d;
+            for (int k = 0; k < 9; ++k) {
+                Vn[k] = (c_v * V[k] + c_f * gW[k]) + dt * gW[k];
+                const double d = dt * Vn[k];
+                s2_c += d * d;
+            }
+            s2[0] += s2_c;
         }
-        s2[0] += s2_c;
-    }
     const double s = sqrt(s2[0]);
     const double clip = s > c.maxstep ? c.maxstep / s : 1.0;
 
     if (!free_cell) {
-        // pass 3 of fire_step_kernel; s follows pos (F = I)
+        // pass 3: pos += dt v (clipped); every lane re-reads the velocities it wrote itself.  With a cell, s follows pos (F = I)
+        // (an atom's three loads stand before its stores: pos and vel are not known to be distinct, and would be read one by one)
         for (int64_t i = n0 + threadIdx.x; i < n1; i += FIRE_THREADS) {
+            double px = a.pos[i * 3 + 0], py = a.pos[i * 3 + 1], pz = a.pos[i * 3 + 2];
             if (!(fixed && fixed[i])) {
-                a.pos[i * 3 + 0] = __builtin_fma(clip, dt * vel[i * 3 + 0], a.pos[i * 3 + 0]);
-                a.pos[i * 3 + 1] = __builtin_fma(clip, dt * vel[i * 3 + 1], a.pos[i * 3 + 1]);
-                a.pos[i * 3 + 2] = __builtin_fma(clip, dt * vel[i * 3 + 2], a.pos[i * 3 + 2]);
+                px = __builtin_fma(clip, dt * vel[i * 3 + 0], px);
+                py = __builtin_fma(clip, dt * vel[i * 3 + 1], py);
+                pz = __builtin_fma(clip, dt * vel[i * 3 + 2], pz);
+                a.pos[i * 3 + 0] = px;
+                a.pos[i * 3 + 1] = py;
+                a.pos[i * 3 + 2] = pz;
             }
-            a.scaled[i * 3 + 0] = a.pos[i * 3 + 0];
-            a.scaled[i * 3 + 1] = a.pos[i * 3 + 1];
-            a.scaled[i * 3 + 2] = a.pos[i * 3 + 2];
+            if constexpr (CELL) {
+                a.scaled[i * 3 + 0] = px;
+                a.scaled[i * 3 + 1] = py;
+                a.scaled[i * 3 + 2] = pz;
+            }
         }
-    } else {
+    } else if constexpr (CELL) {
         // W += clip dt v_W, F' = W / cf; the trust region decides before anything is written
         double dev2 = 0.0;
 #pragma unroll
@@ -423,16 +348,29 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_cell_step_kernel(FireCellAr
         a.alpha[b] = alpha;
         a.n_pos[b] = n_pos;
         a.steps[b] = steps + 1;
-        if (free_cell) {
-            for (int k = 0; k < 9; ++k) {
-                a.deform[b * 9 + k] = Fn[k];
-                a.vel_cell[b * 9 + k] = Vn[k];
+        if constexpr (CELL)
+            if (free_cell) {
+                for (int k = 0; k < 9; ++k) {
+                    a.deform[b * 9 + k] = Fn[k];
+                    a.vel_cell[b * 9 + k] = Vn[k];
+                }
+                for (int r = 0; r < 3; ++r)                    // cell = C0 F'^T: lattice vector r is F' a0_r
+                    for (int q = 0; q < 3; ++q)
+                        a.cell[b * 9 + r * 3 + q] = m_C0[r * 3 + 0] * Fn[q * 3 + 0] + m_C0[r * 3 + 1] * Fn[q * 3 + 1] + m_C0[r * 3 + 2] * Fn[q * 3 + 2];
             }
-            for (int r = 0; r < 3; ++r)                        // cell = C0 F'^T: lattice vector r is F' a0_r
-                for (int q = 0; q < 3; ++q)
-                    a.cell[b * 9 + r * 3 + q] = m_C0[r * 3 + 0] * Fn[q * 3 + 0] + m_C0[r * 3 + 1] * Fn[q * 3 + 1] + m_C0[r * 3 + 2] * Fn[q * 3 + 2];
-        }
     }
+}
+
+// what both entry points ask of N, B and FIRE's constants; an empty batch (N == 0) launches nothing and has no grid to overflow
+int fire_check(const char* fn, int64_t N, int64_t B, const FireConst& c) {
+    MDL_REQUIRE(N >= 0 && B >= 0, MDL_E_ARG, "%s: bad N=%lld B=%lld", fn, (long long)N, (long long)B);
+    MDL_REQUIRE(c.n_min >= 0 && c.f_inc > 0.0 && c.f_dec > 0.0 && c.f_alpha > 0.0 && c.alpha_start >= 0.0 && c.alpha_start <= 1.0 &&
+                    c.dt_max > 0.0 && c.maxstep > 0.0,
+                MDL_E_ARG, "%s: need n_min >= 0, f_inc, f_dec, f_alpha, dt_max, maxstep > 0 and alpha_start in [0, 1] "
+                           "(got n_min=%d f_inc=%g f_dec=%g f_alpha=%g alpha_start=%g dt_max=%g maxstep=%g)",
+                fn, (int)c.n_min, c.f_inc, c.f_dec, c.f_alpha, c.alpha_start, c.dt_max, c.maxstep);
+    MDL_REQUIRE(N == 0 || B < (1ll << 31), MDL_E_UNSUPP, "%s: B=%lld structures overflow the grid", fn, (long long)B);
+    return MDL_OK;
 }
 
 }  // namespace
@@ -446,22 +384,16 @@ extern "C" int mdl_fire_cell_step(double* pos, double* cell, double* scaled, dou
                                   double alpha_start, double f_alpha, double dt_max, double maxstep, double max_deform,
                                   mdlStream_t stream) {
     using namespace mdl;
-    MDL_REQUIRE(N >= 0 && B >= 0, MDL_E_ARG, "mdl_fire_cell_step: bad N=%lld B=%lld", (long long)N, (long long)B);
-    MDL_REQUIRE(n_min >= 0 && f_inc > 0.0 && f_dec > 0.0 && f_alpha > 0.0 && alpha_start >= 0.0 && alpha_start <= 1.0 && dt_max > 0.0 &&
-                    maxstep > 0.0,
-                MDL_E_ARG, "mdl_fire_cell_step: need n_min >= 0, f_inc, f_dec, f_alpha, dt_max, maxstep > 0 and alpha_start in [0, 1] "
-                           "(got n_min=%d f_inc=%g f_dec=%g f_alpha=%g alpha_start=%g dt_max=%g maxstep=%g)",
-                (int)n_min, f_inc, f_dec, f_alpha, alpha_start, dt_max, maxstep);
+    const FireConst c = {n_min, f_inc, f_dec, alpha_start, f_alpha, dt_max, maxstep};
+    if (const int err = fire_check("mdl_fire_cell_step", N, B, c)) return err;
     MDL_REQUIRE(max_deform > 0.0 && max_deform < 1.0, MDL_E_ARG, "mdl_fire_cell_step: max_deform must be in (0, 1) (got %g)", max_deform);
     if (B == 0 || N == 0) return MDL_OK;
-    MDL_REQUIRE(B < (1ll << 31), MDL_E_UNSUPP, "mdl_fire_cell_step: B=%lld structures overflow the grid", (long long)B);
     MDL_REQUIRE(pos && cell && scaled && deform && vel && vel_cell && force && strain_grad && cell0 && cell_free && cell_factor &&
                     node_ptr && fmax && smax && dt && alpha && n_pos && steps && done && fmax_seen && smax_seen,
                 MDL_E_ARG, "mdl_fire_cell_step: null pointer");
-    const FireConst c = {n_min, f_inc, f_dec, alpha_start, f_alpha, dt_max, maxstep};
-    const FireCellArgs a = {pos,  cell, scaled, deform, vel,   vel_cell, force, strain_grad, cell0, fixed,     cell_free, cell_factor,
-                            node_ptr, N, fmax,  smax,   dt,    alpha,    n_pos, steps,       done,  fmax_seen, smax_seen};
-    hipLaunchKernelGGL(fire_cell_step_kernel, dim3((unsigned)B), dim3(FIRE_THREADS), 0, (hipStream_t)stream, a, c, max_deform);
+    const FireArgs a = {pos,  vel,    force,  fixed,    node_ptr,    N,     fmax,      dt,          alpha, n_pos,    steps, done, fmax_seen,
+                        cell, scaled, deform, vel_cell, strain_grad, cell0, cell_free, cell_factor, smax,  smax_seen};
+    hipLaunchKernelGGL(fire_kernel<true>, dim3((unsigned)B), dim3(FIRE_THREADS), 0, (hipStream_t)stream, a, c, max_deform);
     return check_launch("mdl_fire_cell_step");
 }
 
@@ -470,18 +402,12 @@ extern "C" int mdl_fire_step(double* pos, double* vel, const float* force, const
                              float* fmax_seen, int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha,
                              double dt_max, double maxstep, mdlStream_t stream) {
     using namespace mdl;
-    MDL_REQUIRE(N >= 0 && B >= 0, MDL_E_ARG, "mdl_fire_step: bad N=%lld B=%lld", (long long)N, (long long)B);
-    MDL_REQUIRE(n_min >= 0 && f_inc > 0.0 && f_dec > 0.0 && f_alpha > 0.0 && alpha_start >= 0.0 && alpha_start <= 1.0 && dt_max > 0.0 &&
-                    maxstep > 0.0,
-                MDL_E_ARG, "mdl_fire_step: need n_min >= 0, f_inc, f_dec, f_alpha, dt_max, maxstep > 0 and alpha_start in [0, 1] "
-                           "(got n_min=%d f_inc=%g f_dec=%g f_alpha=%g alpha_start=%g dt_max=%g maxstep=%g)",
-                (int)n_min, f_inc, f_dec, f_alpha, alpha_start, dt_max, maxstep);
+    const FireConst c = {n_min, f_inc, f_dec, alpha_start, f_alpha, dt_max, maxstep};
+    if (const int err = fire_check("mdl_fire_step", N, B, c)) return err;
     if (B == 0 || N == 0) return MDL_OK;
-    MDL_REQUIRE(B < (1ll << 31), MDL_E_UNSUPP, "mdl_fire_step: B=%lld structures overflow the grid", (long long)B);
     MDL_REQUIRE(pos && vel && force && node_ptr && fmax && dt && alpha && n_pos && steps && done && fmax_seen, MDL_E_ARG,
                 "mdl_fire_step: null pointer");
-    const FireConst c = {n_min, f_inc, f_dec, alpha_start, f_alpha, dt_max, maxstep};
-    hipLaunchKernelGGL(fire_step_kernel, dim3((unsigned)B), dim3(FIRE_THREADS), 0, (hipStream_t)stream, pos, vel, force, fixed, node_ptr, N,
-                       fmax, dt, alpha, n_pos, steps, done, fmax_seen, c);
+    const FireArgs a = {pos, vel, force, fixed, node_ptr, N, fmax, dt, alpha, n_pos, steps, done, fmax_seen};   // the cell's fields: null
+    hipLaunchKernelGGL(fire_kernel<false>, dim3((unsigned)B), dim3(FIRE_THREADS), 0, (hipStream_t)stream, a, c, 0.0);
     return check_launch("mdl_fire_step");
 }

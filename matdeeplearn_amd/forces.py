@@ -125,10 +125,15 @@ def _per_volume(strain, cell, pbc):
     a, b, c = cell[:, 0], cell[:, 1], cell[:, 2]
     vol = (a[:, 0] * (b[:, 1] * c[:, 2] - b[:, 2] * c[:, 1]) + a[:, 1] * (b[:, 2] * c[:, 0] - b[:, 0] * c[:, 2])
            + a[:, 2] * (b[:, 0] * c[:, 1] - b[:, 1] * c[:, 0])).abs()
-    periodic = (pbc != 0).all(1) if pbc.dim() == 2 else (pbc & 7) == 7
-    has_volume = periodic & (vol > 0)
+    has_volume = _periodic_with_volume(pbc, vol)
     inv = torch.where(has_volume, 1.0 / torch.where(has_volume, vol, torch.ones_like(vol)), torch.full_like(vol, float("nan")))
     return (strain.double() * inv.view(-1, 1, 1)).float()
+
+
+def _periodic_with_volume(pbc, vol):
+    """[B] bool: the structures that have a stress, and whose cell relax_cell may move — periodic along all three axes (pbc [B, 3],
+    or [B] with one bit per axis) and with a cell volume vol [B] > 0"""
+    return ((pbc != 0).all(1) if pbc.dim() == 2 else (pbc & 7) == 7) & (vol > 0)
 
 
 def _accepted(model, dist_range):
@@ -352,45 +357,9 @@ def relax(model, structs, dist_range, fmax=0.05, steps=200, rebuild_every=1, fix
     Returns RelaxResult(positions [N, 3] float64, energy [B] or [B, out] fp32, forces [N, 3] fp32, converged [B] bool, steps [B]
     int32 (updates made per structure), fmax [B] fp32 (largest per-atom force on a free atom), node_ptr), device tensors.  With
     ops.deterministic() two calls return the same bits: the integrator itself has no atomics."""
-    _accepted(model, dist_range)
-    if model.training:
-        raise ops.MdlError("relax: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
-                           "(and dropout makes the energy a random function)")
-    steps, rebuild_every, check_every = int(steps), int(rebuild_every), int(check_every)
-    if steps < 0 or rebuild_every < 0 or check_every < 0:
-        raise ops.MdlError("relax: steps, rebuild_every and check_every must be >= 0")
-    ff = ForceField(model, structs, dist_range, radius, max_neighbors, dictionary, output_index)
-    dev, N, B = ff.positions.device, ff.positions.shape[0], ff.node_ptr.numel() - 1
-    if torch.is_tensor(fmax) or np.ndim(fmax) > 0:
-        fmax_t = (fmax.detach() if torch.is_tensor(fmax) else torch.from_numpy(np.asarray(fmax, dtype=np.float64))).to(dev, torch.float64)
-        if tuple(fmax_t.shape) != (B,):
-            raise ops.MdlError("relax: fmax must be a number or one value per structure, [%d] (got %s)" % (B, tuple(fmax_t.shape)))
-    else:
-        fmax_t = torch.full((B,), float(fmax), dtype=torch.float64, device=dev)
-    if fixed is not None:
-        fixed = (fixed.detach() if torch.is_tensor(fixed) else torch.from_numpy(np.asarray(fixed))).to(dev)
-        if tuple(fixed.shape) != (N,):
-            raise ops.MdlError("relax: fixed must be an [N] mask with N = %d (got %s)" % (N, tuple(fixed.shape)))
-        fixed = (fixed != 0).to(torch.uint8)
     const = dict(n_min=n_min, f_inc=f_inc, f_dec=f_dec, alpha_start=alpha, f_alpha=f_alpha, dt_max=dt_max, maxstep=maxstep)
-    state = ops.fire_state(B, dt, alpha, dev)
-    vel = torch.zeros_like(ff.positions)
-    n_eval = 0
-    for it in range(steps):
-        if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
-            ff.rebuild()
-        _, f = ff.evaluate()
-        n_eval += 1
-        ops.fire_step(ff.positions, vel, f, ff.node_ptr, state, fmax_t, fixed, **const)
-        if check_every > 0 and (it + 1) % check_every == 0 and bool(state.done.all()):
-            break
-    if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
-        ff.rebuild()
-    energy, f = ff.evaluate()
-    # the largest force at the returned positions, from the integrator's own pass 1: with every latch set nothing else is written
-    probe = state.clone()
-    probe.done.fill_(1)
-    ops.fire_step(ff.positions, vel, f, ff.node_ptr, probe, fmax_t, fixed, **const)
+    ff, state, probe, (fmax_t,), (energy, f) = _relax("relax", model, structs, dist_range, (("fmax", fmax),), steps, rebuild_every, check_every,
+                                                      fixed, dt, const, (radius, max_neighbors, dictionary, output_index))
     converged = (state.done != 0) | (probe.fmax_seen.double() < fmax_t)
     return RelaxResult(ff.positions, energy, f, converged, state.steps, probe.fmax_seen, ff.node_ptr)
 
@@ -398,14 +367,78 @@ def relax(model, structs, dist_range, fmax=0.05, steps=200, rebuild_every=1, fix
 CellRelaxResult = collections.namedtuple("CellRelaxResult", "positions cell energy forces stress converged steps fmax smax status node_ptr")
 
 
-def _per_structure(v, B, dev, what):
+def _per_structure(v, B, dev, who, what):
     """a number or one value per structure -> [B] float64 on the device"""
     if torch.is_tensor(v) or np.ndim(v) > 0:
         t = (v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, dtype=np.float64))).to(dev, torch.float64)
         if tuple(t.shape) != (B,):
-            raise ops.MdlError("relax_cell: %s must be a number or one value per structure, [%d] (got %s)" % (what, B, tuple(t.shape)))
+            raise ops.MdlError("%s: %s must be a number or one value per structure, [%d] (got %s)" % (who, what, B, tuple(t.shape)))
         return t.contiguous()
     return torch.full((B,), float(v), dtype=torch.float64, device=dev)
+
+
+def _relax(who, model, structs, dist_range, bounds, steps, rebuild_every, check_every, fixed, dt, const, ff_args, cell=None):
+    """relax and relax_cell (`who`) behind their arguments: the checks, the ForceField, the rebuild / evaluate / step loop and the
+    evaluation at the returned geometry.  bounds: ((name, value), ...) of the convergence criteria; const: the constants of the
+    step; cell: None (ops.fire_step on the forces alone), or relax_cell's (cell_free, cell_factor) (ops.fire_cell_step on forces
+    and strain gradient).  Returns (the ForceField, the state, a probe — a copy of the state with every latch set, stepped once
+    at the returned geometry: with every latch set the integrator writes its criteria from its own pass 1 and nothing else —, the
+    bounds as [B] float64 tensors, what that last evaluation returned)."""
+    _accepted(model, dist_range)
+    if model.training:
+        raise ops.MdlError("%s: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
+                           "(and dropout makes the energy a random function)" % who)
+    steps, rebuild_every, check_every = int(steps), int(rebuild_every), int(check_every)
+    if steps < 0 or rebuild_every < 0 or check_every < 0:
+        raise ops.MdlError("%s: steps, rebuild_every and check_every must be >= 0" % who)
+    if cell is not None and not 0.0 < float(const["max_deform"]) < 1.0:
+        raise ops.MdlError("%s: max_deform must be in (0, 1) (got %r)" % (who, const["max_deform"]))
+    ff = ForceField(model, structs, dist_range, *ff_args)
+    dev, N, B = ff.positions.device, ff.positions.shape[0], ff.node_ptr.numel() - 1
+    bounds = [_per_structure(v, B, dev, who, name) for name, v in bounds]
+    if fixed is not None:
+        fixed = (fixed.detach() if torch.is_tensor(fixed) else torch.from_numpy(np.asarray(fixed))).to(dev)
+        if tuple(fixed.shape) != (N,):
+            raise ops.MdlError("%s: fixed must be an [N] mask with N = %d (got %s)" % (who, N, tuple(fixed.shape)))
+        fixed = (fixed != 0).to(torch.uint8)
+    if cell is None:
+        state = ops.fire_state(B, dt, const["alpha_start"], dev)
+    else:
+        cell_free, cell_factor = cell
+        c = ff.cell
+        free = _periodic_with_volume(ff.pbc, (c[:, 0] * torch.linalg.cross(c[:, 1], c[:, 2])).sum(1).abs())
+        if cell_free is not None:
+            mask = (cell_free.detach() if torch.is_tensor(cell_free) else torch.from_numpy(np.asarray(cell_free))).to(dev)
+            if tuple(mask.shape) != (B,):
+                raise ops.MdlError("%s: cell_free must be a [B] mask with B = %d (got %s)" % (who, B, tuple(mask.shape)))
+            free = free & (mask != 0)
+        if cell_factor is not None:
+            cell_factor = _per_structure(cell_factor, B, dev, who, "cell_factor")
+        state = ops.fire_cell_state(ff.positions, ff.cell, ff.node_ptr, free, cell_factor, dt, const["alpha_start"])
+    vel = torch.zeros_like(ff.positions)
+    n_eval = 0
+
+    def advance(st):
+        """the lists rebuilt when due, one evaluation, one update of `st`"""
+        nonlocal n_eval
+        if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
+            ff.rebuild()
+        n_eval += 1
+        if cell is None:
+            out = ff.evaluate()
+            ops.fire_step(ff.positions, vel, out[1], ff.node_ptr, st, *bounds, fixed, **const)
+        else:
+            out = ff.evaluate(stress=True, volume_normalised=False)
+            ops.fire_cell_step(ff.positions, ff.cell, vel, out[1], out[2], ff.node_ptr, st, *bounds, fixed, **const)
+        return out
+
+    for it in range(steps):
+        advance(state)
+        if check_every > 0 and (it + 1) % check_every == 0 and bool(state.done.all()):
+            break
+    probe = state.clone()
+    probe.done.fill_(1)
+    return ff, state, probe, bounds, advance(probe)
 
 
 def relax_cell(model, structs, dist_range, fmax=0.05, smax=1e-3, steps=200, rebuild_every=1, fixed=None, cell_free=None, cell_factor=None,
@@ -437,53 +470,11 @@ def relax_cell(model, structs, dist_range, fmax=0.05, smax=1e-3, steps=200, rebu
     bool, steps [B] int32, fmax [B] fp32, smax [B] fp32 (max |stress| at the returned geometry; NaN where stress is), status [B]
     int32 (0 still moving, 1 converged, 2 stopped by the trust region), node_ptr), device tensors.  With ops.deterministic() two
     calls return the same bits."""
-    _accepted(model, dist_range)
-    if model.training:
-        raise ops.MdlError("relax_cell: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
-                           "(and dropout makes the energy a random function)")
-    steps, rebuild_every, check_every = int(steps), int(rebuild_every), int(check_every)
-    if steps < 0 or rebuild_every < 0 or check_every < 0:
-        raise ops.MdlError("relax_cell: steps, rebuild_every and check_every must be >= 0")
-    if not 0.0 < float(max_deform) < 1.0:
-        raise ops.MdlError("relax_cell: max_deform must be in (0, 1) (got %r)" % (max_deform,))
-    ff = ForceField(model, structs, dist_range, radius, max_neighbors, dictionary, output_index)
-    dev, N, B = ff.positions.device, ff.positions.shape[0], ff.node_ptr.numel() - 1
-    fmax_t, smax_t = _per_structure(fmax, B, dev, "fmax"), _per_structure(smax, B, dev, "smax")
-    if fixed is not None:
-        fixed = (fixed.detach() if torch.is_tensor(fixed) else torch.from_numpy(np.asarray(fixed))).to(dev)
-        if tuple(fixed.shape) != (N,):
-            raise ops.MdlError("relax_cell: fixed must be an [N] mask with N = %d (got %s)" % (N, tuple(fixed.shape)))
-        fixed = (fixed != 0).to(torch.uint8)
-    c = ff.cell
-    vol = (c[:, 0] * torch.linalg.cross(c[:, 1], c[:, 2])).sum(1).abs()
-    free = ((ff.pbc != 0).all(1) if ff.pbc.dim() == 2 else (ff.pbc & 7) == 7) & (vol > 0)
-    if cell_free is not None:
-        mask = (cell_free.detach() if torch.is_tensor(cell_free) else torch.from_numpy(np.asarray(cell_free))).to(dev)
-        if tuple(mask.shape) != (B,):
-            raise ops.MdlError("relax_cell: cell_free must be a [B] mask with B = %d (got %s)" % (B, tuple(mask.shape)))
-        free = free & (mask != 0)
-    if cell_factor is not None:
-        cell_factor = _per_structure(cell_factor, B, dev, "cell_factor")
     const = dict(n_min=n_min, f_inc=f_inc, f_dec=f_dec, alpha_start=alpha, f_alpha=f_alpha, dt_max=dt_max, maxstep=maxstep,
                  max_deform=max_deform)
-    state = ops.fire_cell_state(ff.positions, ff.cell, ff.node_ptr, free, cell_factor, dt, alpha)
-    vel = torch.zeros_like(ff.positions)
-    n_eval = 0
-    for it in range(steps):
-        if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
-            ff.rebuild()
-        _, f, strain = ff.evaluate(stress=True, volume_normalised=False)
-        n_eval += 1
-        ops.fire_cell_step(ff.positions, ff.cell, vel, f, strain, ff.node_ptr, state, fmax_t, smax_t, fixed, **const)
-        if check_every > 0 and (it + 1) % check_every == 0 and bool(state.done.all()):
-            break
-    if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
-        ff.rebuild()
-    energy, f, strain = ff.evaluate(stress=True, volume_normalised=False)
-    # the criteria at the returned geometry, from the integrator's own pass 1: with every latch set nothing else is written
-    probe = state.clone()
-    probe.done.fill_(1)
-    ops.fire_cell_step(ff.positions, ff.cell, vel, f, strain, ff.node_ptr, probe, fmax_t, smax_t, fixed, **const)
+    ff, state, probe, (fmax_t, smax_t), (energy, f, strain) = _relax(
+        "relax_cell", model, structs, dist_range, (("fmax", fmax), ("smax", smax)), steps, rebuild_every, check_every, fixed, dt, const,
+        (radius, max_neighbors, dictionary, output_index), (cell_free, cell_factor))
     fm, sm = probe.fmax_seen.double(), probe.smax_seen.double()
     met = ((fm < fmax_t) | ~(fm > 0)) & ((state.cell_free == 0) | (sm < smax_t) | ~(sm > 0))
     converged = (state.done == 1) | met

@@ -2773,56 +2773,6 @@ def fire_state(B, dt=0.1, alpha=0.1, device=None):
                      torch.zeros(int(B), dtype=torch.float32, device=dev))
 
 
-def fire_step(pos, vel, force, node_ptr, state, fmax, fixed=None, **constants):
-    """One FIRE update (unit masses) of every structure of a batch, in place, in ONE launch.
-      pos, vel [N, 3] float64 (updated in place: contiguous tensors), force [N, 3] float32, node_ptr [B + 1] int64, state a
-      FireState of B structures (updated in place), fmax a number or a [B] float64 tensor, fixed [N] uint8 / bool or None
-      (non-zero: the atom stays where it is), constants: any of FIRE_CONSTANTS (n_min, f_inc, f_dec, alpha_start, f_alpha,
-      dt_max, maxstep).
-    A structure whose largest per-atom force is below its fmax — or that converged in an earlier call, or has no force on a free
-    atom — gets state.done = 1 and is otherwise left alone: positions, velocities and the rest of its state keep their bits.
-    The others move as include/mdl_hip.h (mdl_fire_step) states it.  No host synchronisation, no atomics: two calls from the same
-    inputs give the same bits.  Returns state."""
-    unknown = set(constants) - set(FIRE_CONSTANTS)
-    if unknown:
-        raise MdlError("fire_step: unknown constants %s (known: %s)" % (sorted(unknown), sorted(FIRE_CONSTANTS)))
-    c = dict(FIRE_CONSTANTS, **constants)
-    if not isinstance(state, FireState):
-        raise MdlError("fire_step: state must be an ops.FireState (ops.fire_state)")
-    require_hip(pos, vel, force, node_ptr, fixed, *[getattr(state, k) for k in FireState.__slots__])
-    N = pos.shape[0] if pos.dim() == 2 else -1
-    for name, t in (("pos", pos), ("vel", vel)):
-        if t.dtype != torch.float64 or tuple(t.shape) != (N, 3) or not t.is_contiguous():
-            raise MdlError("fire_step: %s must be a contiguous [N, 3] float64 tensor (got %s %s)" % (name, tuple(t.shape), t.dtype))
-    if force.dtype != torch.float32 or tuple(force.shape) != (N, 3):
-        raise MdlError("fire_step: force must be [N, 3] float32 with N = %d (got %s %s)" % (N, tuple(force.shape), force.dtype))
-    if node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 1:
-        raise MdlError("fire_step: node_ptr must be [B + 1] int64")
-    B = node_ptr.numel() - 1
-    for k, dt_ in (("dt", torch.float64), ("alpha", torch.float64), ("n_pos", torch.int32), ("steps", torch.int32), ("done", torch.int32),
-                   ("fmax_seen", torch.float32)):
-        t = getattr(state, k)
-        if t.dtype != dt_ or tuple(t.shape) != (B,) or not t.is_contiguous():
-            raise MdlError("fire_step: state.%s must be a contiguous [B] %s tensor with B = %d (got %s %s)" % (k, dt_, B, tuple(t.shape), t.dtype))
-    if torch.is_tensor(fmax):
-        if fmax.dtype != torch.float64 or tuple(fmax.shape) != (B,):
-            raise MdlError("fire_step: fmax must be a number or a [B] float64 tensor with B = %d (got %s %s)" % (B, tuple(fmax.shape), fmax.dtype))
-        require_hip(fmax)
-    else:
-        fmax = torch.full((B,), float(fmax), dtype=torch.float64, device=pos.device)
-    if fixed is not None:
-        if fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
-            raise MdlError("fire_step: fixed must be [N] uint8 or bool with N = %d (got %s %s)" % (N, tuple(fixed.shape), fixed.dtype))
-        fixed = fixed.contiguous().view(torch.uint8)
-    if any(t.device != pos.device for t in (vel, force, node_ptr, fmax, state.dt) if t is not None):
-        raise MdlError("fire_step: pos, vel, force, node_ptr, fmax and the state must be on one device")
-    check(lib().mdl_fire_step(ptr(pos), ptr(vel), ptr(force.contiguous()), ptr(fixed), ptr(node_ptr.contiguous()), N, B, ptr(fmax.contiguous()),
-                              ptr(state.dt), ptr(state.alpha), ptr(state.n_pos), ptr(state.steps), ptr(state.done), ptr(state.fmax_seen),
-                              int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
-                              float(c["dt_max"]), float(c["maxstep"]), stream()), "mdl_fire_step")
-    return state
-
-
 class FireCellState:
     """Per-structure state of fire_cell_step: the FireState fields ([B]: dt, alpha, n_pos, steps, done, fmax_seen) and what the
     cell's degrees of freedom add — scaled [N, 3] float64 (s: pos_i = F s_i), deform [B, 3, 3] float64 (F: cell = cell0 F^T),
@@ -2842,11 +2792,82 @@ class FireCellState:
         return FireCellState(*[getattr(self, k).clone() for k in self.__slots__])
 
 
+# (field, dtype, shape behind [B]) of the state: the first six are FireState's
 _FIRE_CELL_FIELDS = (("dt", torch.float64, ()), ("alpha", torch.float64, ()), ("n_pos", torch.int32, ()), ("steps", torch.int32, ()),
                      ("done", torch.int32, ()), ("fmax_seen", torch.float32, ()), ("deform", torch.float64, (3, 3)),
                      ("vel_cell", torch.float64, (3, 3)), ("cell0", torch.float64, (3, 3)), ("cell_free", torch.uint8, ()),
                      ("cell_factor", torch.float64, ()), ("smax_seen", torch.float32, ()))
 FIRE_CELL_CONSTANTS = dict(FIRE_CONSTANTS, max_deform=0.5)
+# entry point -> (its constants, its state, what makes one, the state's [B, ...] fields)
+_FIRE_KINDS = {"fire_step": (FIRE_CONSTANTS, FireState, "fire_state", _FIRE_CELL_FIELDS[:len(FireState.__slots__)]),
+               "fire_cell_step": (FIRE_CELL_CONSTANTS, FireCellState, "fire_cell_state", _FIRE_CELL_FIELDS)}
+
+
+def _fire_args(who, pos, vel, force, node_ptr, state, bounds, fixed, constants, cell=None, strain_grad=None):
+    """The argument checks of fire_step and fire_cell_step (`who`: the name every message starts with; cell and strain_grad belong
+    to fire_cell_step alone; bounds: (name, a number or a [B] float64 tensor) each).  Returns (the constants with their defaults,
+    N, B, the bounds as contiguous [B] float64 device tensors, fixed as contiguous uint8 or None)."""
+    known, state_type, maker, fields = _FIRE_KINDS[who]
+    unknown = set(constants) - set(known)
+    if unknown:
+        raise MdlError("%s: unknown constants %s (known: %s)" % (who, sorted(unknown), sorted(known)))
+    c = dict(known, **constants)
+    if not isinstance(state, state_type):
+        raise MdlError("%s: state must be an ops.%s (ops.%s)" % (who, state_type.__name__, maker))
+    with_cell = state_type is FireCellState
+    require_hip(pos, cell, vel, force, strain_grad, node_ptr, fixed, *[getattr(state, k) for k in state_type.__slots__])
+    N = pos.shape[0] if pos.dim() == 2 else -1
+    for name, t in (("pos", pos), ("vel", vel)) + ((("state.scaled", state.scaled),) if with_cell else ()):
+        if t.dtype != torch.float64 or tuple(t.shape) != (N, 3) or not t.is_contiguous():
+            raise MdlError("%s: %s must be a contiguous [N, 3] float64 tensor (got %s %s)" % (who, name, tuple(t.shape), t.dtype))
+    if force.dtype != torch.float32 or tuple(force.shape) != (N, 3):
+        raise MdlError("%s: force must be [N, 3] float32 with N = %d (got %s %s)" % (who, N, tuple(force.shape), force.dtype))
+    if node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 1:
+        raise MdlError("%s: node_ptr must be [B + 1] int64" % who)
+    B = node_ptr.numel() - 1
+    if with_cell:
+        if cell.dtype != torch.float64 or tuple(cell.shape) != (B, 3, 3) or not cell.is_contiguous():
+            raise MdlError("%s: cell must be a contiguous [B, 3, 3] float64 tensor with B = %d (got %s %s)" % (who, B, tuple(cell.shape), cell.dtype))
+        if strain_grad.dtype != torch.float32 or tuple(strain_grad.shape) != (B, 3, 3):
+            raise MdlError("%s: strain_grad must be [B, 3, 3] float32 with B = %d (got %s %s)" % (who, B, tuple(strain_grad.shape), strain_grad.dtype))
+    for k, dt_, tail in fields:
+        t = getattr(state, k)
+        if t.dtype != dt_ or tuple(t.shape) != (B,) + tail or not t.is_contiguous():
+            raise MdlError("%s: state.%s must be a contiguous %s %s tensor with B = %d (got %s %s)" % (who, k, list((B,) + tail), dt_, B, tuple(t.shape), t.dtype))
+    out = []
+    for name, v in bounds:
+        if torch.is_tensor(v):
+            if v.dtype != torch.float64 or tuple(v.shape) != (B,):
+                raise MdlError("%s: %s must be a number or a [B] float64 tensor with B = %d (got %s %s)" % (who, name, B, tuple(v.shape), v.dtype))
+            require_hip(v)
+            out.append(v.contiguous())
+        else:
+            out.append(torch.full((B,), float(v), dtype=torch.float64, device=pos.device))
+    if fixed is not None:
+        if fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
+            raise MdlError("%s: fixed must be [N] uint8 or bool with N = %d (got %s %s)" % (who, N, tuple(fixed.shape), fixed.dtype))
+        fixed = fixed.contiguous().view(torch.uint8)
+    if any(t.device != pos.device for t in [vel, force, node_ptr, state.dt] + out + ([cell, strain_grad, state.scaled] if with_cell else [])):
+        raise MdlError("%s: pos, the other tensors (%s among them) and the state must be on one device" % (who, ", ".join(n for n, _ in bounds)))
+    return c, N, B, out, fixed
+
+
+def fire_step(pos, vel, force, node_ptr, state, fmax, fixed=None, **constants):
+    """One FIRE update (unit masses) of every structure of a batch, in place, in ONE launch.
+      pos, vel [N, 3] float64 (updated in place: contiguous tensors), force [N, 3] float32, node_ptr [B + 1] int64, state a
+      FireState of B structures (updated in place), fmax a number or a [B] float64 tensor, fixed [N] uint8 / bool or None
+      (non-zero: the atom stays where it is), constants: any of FIRE_CONSTANTS (n_min, f_inc, f_dec, alpha_start, f_alpha,
+      dt_max, maxstep).
+    A structure whose largest per-atom force is below its fmax — or that converged in an earlier call, or has no force on a free
+    atom — gets state.done = 1 and is otherwise left alone: positions, velocities and the rest of its state keep their bits.
+    The others move as include/mdl_hip.h (mdl_fire_step) states it.  No host synchronisation, no atomics: two calls from the same
+    inputs give the same bits.  Returns state."""
+    c, N, B, (fmax,), fixed = _fire_args("fire_step", pos, vel, force, node_ptr, state, (("fmax", fmax),), fixed, constants)
+    check(lib().mdl_fire_step(ptr(pos), ptr(vel), ptr(force.contiguous()), ptr(fixed), ptr(node_ptr.contiguous()), N, B, ptr(fmax),
+                              ptr(state.dt), ptr(state.alpha), ptr(state.n_pos), ptr(state.steps), ptr(state.done), ptr(state.fmax_seen),
+                              int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
+                              float(c["dt_max"]), float(c["maxstep"]), stream()), "mdl_fire_step")
+    return state
 
 
 def fire_cell_state(pos, cell, node_ptr, cell_free=None, cell_factor=None, dt=0.1, alpha=0.1):
@@ -2892,48 +2913,11 @@ def fire_cell_step(pos, cell, vel, force, strain_grad, node_ptr, state, fmax, sm
     Coordinates, generalised forces, the convergence rule (max_i |F_i| < fmax AND, where the cell is free, max |dE/d eps| / volume <
     smax), the trust region (state.done = 2) and the frozen-cell case (the bits of fire_step) are stated in include/mdl_hip.h
     (mdl_fire_cell_step).  No host synchronisation, no atomics: two calls from the same inputs give the same bits.  Returns state."""
-    unknown = set(constants) - set(FIRE_CELL_CONSTANTS)
-    if unknown:
-        raise MdlError("fire_cell_step: unknown constants %s (known: %s)" % (sorted(unknown), sorted(FIRE_CELL_CONSTANTS)))
-    c = dict(FIRE_CELL_CONSTANTS, **constants)
-    if not isinstance(state, FireCellState):
-        raise MdlError("fire_cell_step: state must be an ops.FireCellState (ops.fire_cell_state)")
-    require_hip(pos, cell, vel, force, strain_grad, node_ptr, fixed, *[getattr(state, k) for k in FireCellState.__slots__])
-    N = pos.shape[0] if pos.dim() == 2 else -1
-    for name, t in (("pos", pos), ("vel", vel), ("state.scaled", state.scaled)):
-        if t.dtype != torch.float64 or tuple(t.shape) != (N, 3) or not t.is_contiguous():
-            raise MdlError("fire_cell_step: %s must be a contiguous [N, 3] float64 tensor (got %s %s)" % (name, tuple(t.shape), t.dtype))
-    if force.dtype != torch.float32 or tuple(force.shape) != (N, 3):
-        raise MdlError("fire_cell_step: force must be [N, 3] float32 with N = %d (got %s %s)" % (N, tuple(force.shape), force.dtype))
-    if node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 1:
-        raise MdlError("fire_cell_step: node_ptr must be [B + 1] int64")
-    B = node_ptr.numel() - 1
-    if cell.dtype != torch.float64 or tuple(cell.shape) != (B, 3, 3) or not cell.is_contiguous():
-        raise MdlError("fire_cell_step: cell must be a contiguous [B, 3, 3] float64 tensor with B = %d (got %s %s)" % (B, tuple(cell.shape), cell.dtype))
-    if strain_grad.dtype != torch.float32 or tuple(strain_grad.shape) != (B, 3, 3):
-        raise MdlError("fire_cell_step: strain_grad must be [B, 3, 3] float32 with B = %d (got %s %s)" % (B, tuple(strain_grad.shape), strain_grad.dtype))
-    for k, dt_, tail in _FIRE_CELL_FIELDS:
-        t = getattr(state, k)
-        if t.dtype != dt_ or tuple(t.shape) != (B,) + tail or not t.is_contiguous():
-            raise MdlError("fire_cell_step: state.%s must be a contiguous %s %s tensor with B = %d (got %s %s)" % (k, list((B,) + tail), dt_, B, tuple(t.shape), t.dtype))
-    bounds = []
-    for name, v in (("fmax", fmax), ("smax", smax)):
-        if torch.is_tensor(v):
-            if v.dtype != torch.float64 or tuple(v.shape) != (B,):
-                raise MdlError("fire_cell_step: %s must be a number or a [B] float64 tensor with B = %d (got %s %s)" % (name, B, tuple(v.shape), v.dtype))
-            require_hip(v)
-            bounds.append(v.contiguous())
-        else:
-            bounds.append(torch.full((B,), float(v), dtype=torch.float64, device=pos.device))
-    if fixed is not None:
-        if fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
-            raise MdlError("fire_cell_step: fixed must be [N] uint8 or bool with N = %d (got %s %s)" % (N, tuple(fixed.shape), fixed.dtype))
-        fixed = fixed.contiguous().view(torch.uint8)
-    if any(t.device != pos.device for t in (cell, vel, force, strain_grad, node_ptr, bounds[0], bounds[1], state.dt, state.scaled)):
-        raise MdlError("fire_cell_step: pos, cell, vel, force, strain_grad, node_ptr, fmax, smax and the state must be on one device")
+    c, N, B, (fmax, smax), fixed = _fire_args("fire_cell_step", pos, vel, force, node_ptr, state, (("fmax", fmax), ("smax", smax)), fixed,
+                                              constants, cell, strain_grad)
     check(lib().mdl_fire_cell_step(ptr(pos), ptr(cell), ptr(state.scaled), ptr(state.deform), ptr(vel), ptr(state.vel_cell), ptr(force.contiguous()),
                                    ptr(strain_grad.contiguous()), ptr(state.cell0), ptr(fixed), ptr(state.cell_free), ptr(state.cell_factor),
-                                   ptr(node_ptr.contiguous()), N, B, ptr(bounds[0]), ptr(bounds[1]), ptr(state.dt), ptr(state.alpha),
+                                   ptr(node_ptr.contiguous()), N, B, ptr(fmax), ptr(smax), ptr(state.dt), ptr(state.alpha),
                                    ptr(state.n_pos), ptr(state.steps), ptr(state.done), ptr(state.fmax_seen), ptr(state.smax_seen),
                                    int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
                                    float(c["dt_max"]), float(c["maxstep"]), float(c["max_deform"]), stream()), "mdl_fire_cell_step")

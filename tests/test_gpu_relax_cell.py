@@ -371,3 +371,21 @@ def test_relax_cell_refuses_what_it_cannot_do():
         ops.fire_cell_step(pos, cell, torch.zeros_like(pos), torch.zeros(pos.shape[0], 3, device=dev()), torch.zeros(2, 3, 3, device=dev()), ptr,
                            state, 0.05, 1e-3, max_deformation=0.2)
     assert torch.equal(pos, t(p["pos"])) and torch.equal(cell, t(p["cell"])) and not state.steps.any()
+
+
+def test_both_fire_steps_name_themselves_when_a_state_field_has_the_wrong_dtype():
+    from matdeeplearn_amd import ops
+    p = tgf._pack(tgf._bulk_structures(2, seed=4, lo=4, hi=8))
+    t = lambda a: torch.from_numpy(a).to(dev())
+    pos, cell, ptr = t(p["pos"]), t(p["cell"]), t(p["node_ptr"])
+    vel, force, strain = torch.zeros_like(pos), torch.zeros(pos.shape[0], 3, device=dev()), torch.zeros(2, 3, 3, device=dev())
+    state, cell_state = ops.fire_state(2), ops.fire_cell_state(pos, cell, ptr)
+    state.n_pos, cell_state.n_pos = state.n_pos.long(), cell_state.n_pos.long()
+    with pytest.raises(ops.MdlError, match=r"^fire_step: state\.n_pos must be a contiguous \[2\] torch\.int32 tensor"):
+        ops.fire_step(pos, vel, force, ptr, state, 0.05)
+    with pytest.raises(ops.MdlError, match=r"^fire_cell_step: state\.n_pos must be a contiguous \[2\] torch\.int32 tensor"):
+        ops.fire_cell_step(pos, cell, vel, force, strain, ptr, cell_state, 0.05, 1e-3)
+    cell_state.n_pos, cell_state.vel_cell = cell_state.n_pos.int(), cell_state.vel_cell.float()
+    with pytest.raises(ops.MdlError, match=r"^fire_cell_step: state\.vel_cell must be a contiguous \[2, 3, 3\] torch\.float64 tensor"):
+        ops.fire_cell_step(pos, cell, vel, force, strain, ptr, cell_state, 0.05, 1e-3)
+    assert torch.equal(pos, t(p["pos"])) and torch.equal(cell, t(p["cell"])) and not cell_state.steps.any()

@@ -462,3 +462,21 @@ def test_cell_relaxation_surface_exists_and_relax_is_what_it_was():
     assert list(sig.parameters)[:11] == ["model", "structs", "dist_range", "fmax", "smax", "steps", "rebuild_every", "fixed", "cell_free",
                                          "cell_factor", "max_deform"]
     assert sig.parameters["max_deform"].default == 0.5 and sig.parameters["rebuild_every"].default == 1
+
+
+def test_both_fire_steps_check_their_arguments_under_their_own_name():
+    """One checker serves ops.fire_step and ops.fire_cell_step; what it finds before it asks for a device is reported with the name of
+    the function that was called (a state field of the wrong dtype is found behind that: tests/test_gpu_relax_cell.py)."""
+    from matdeeplearn_amd import ops
+    pos, cell, ptr = torch.zeros(2, 3, dtype=torch.float64), torch.eye(3, dtype=torch.float64).unsqueeze(0), torch.tensor([0, 2])
+    state, cell_state = ops.FireState(*[torch.zeros(1)] * 6), ops.FireCellState(*[torch.zeros(1)] * 13)
+    step = lambda st, **kw: ops.fire_step(pos, pos.clone(), torch.zeros(2, 3), ptr, st, 0.05, **kw)
+    cell_step = lambda st, **kw: ops.fire_cell_step(pos, cell, pos.clone(), torch.zeros(2, 3), torch.zeros(1, 3, 3), ptr, st, 0.05, 1e-3, **kw)
+    with pytest.raises(ops.MdlError, match=r"^fire_step: unknown constants \['max_deform'\]"):     # the cell's constant is none of fire_step's
+        step(state, max_deform=0.2)
+    with pytest.raises(ops.MdlError, match=r"^fire_cell_step: unknown constants \['max_step'\]"):
+        cell_step(cell_state, max_deform=0.2, max_step=0.1)
+    with pytest.raises(ops.MdlError, match=r"^fire_step: state must be an ops\.FireState \(ops\.fire_state\)"):
+        step(cell_state)
+    with pytest.raises(ops.MdlError, match=r"^fire_cell_step: state must be an ops\.FireCellState \(ops\.fire_cell_state\)"):
+        cell_step(state)
