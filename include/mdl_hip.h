@@ -737,6 +737,43 @@ int mdl_fire_cell_step(double* pos, double* cell, double* scaled, double* deform
                        int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double dt_max, double maxstep,
                        double max_deform, mdlStream_t stream);
 
+/* ---- Molecular dynamics: one BAOAB step of a batch of structures (csrc/md.hip) ----------------
+ * No reference counterpart.  Everything between two force evaluations in ONE launch, one workgroup per structure, all arithmetic
+ * fp64: BAOAB (B: half kick, A: half drift, O: exact Ornstein-Uhlenbeck step) with one force evaluation per step — the closing
+ * kick of step n and B A O A of step n + 1 are one call.  Atoms of structure b: rows node_ptr[b] .. node_ptr[b + 1] - 1 (clamped
+ * to [0, N]).  Units are the caller's: kT in the energy unit of force x length, mass and dt consistent with it.
+ *   pos, vel [N, 3] fp64, in / out;  force [N, 3] fp32, mass [N] fp64 (> 0), fixed [N] uint8 or NULL (non-zero: the atom does not
+ *   move, does not count, and its velocity is written as zero), read;  dt, gamma (friction, 1 / time), kT [B] fp64, seed [B]
+ *   int64, n_steps [B] int32, read;  steps, status [B] int32, in / out;  ekin [B] fp64, written;  max_disp > 0.
+ * Structure b, h = dt / 2, over its free atoms:
+ *   1. status[b] != 0: NOTHING of the structure is written.
+ *   2. steps[b] > 0: v <- v + h f / m, the kick that closes the previous step (at steps == 0 the velocities given belong to the
+ *      positions given).
+ *   3. ekin = 1/2 sum m |v|^2: it belongs to the current positions and to the energy just evaluated, so prediction + ekin is the
+ *      conserved quantity of gamma == 0.
+ *   4. steps[b] == n_steps[b]: v and ekin are written, status = 1 (finished), and that is all.
+ *   5. the candidate: v' = v + h f / m;  x' = x + h v';  gamma > 0: v'' = c1 v' + c2 sqrt(kT / m) xi with c1 = exp(-gamma dt),
+ *      c2 = sqrt(-expm1(-2 gamma dt)), else v'' = v' and no random number is drawn;  x'' = x' + h v''.
+ *   6. n_bad = the number of free atoms with !(|x'' - x| <= max_disp) — a count, summed: a NaN cannot vanish in it.  n_bad > 0:
+ *      the v of item 2 and ekin are written, status = 2 (refused), the positions keep their bits.  No non-finite position and no
+ *      jump across a neighbour shell ever reaches the next evaluation.
+ *   7. else x'' and v'' are written and steps += 1.
+ * xi: Philox4x32-10, key = (low, high) 32 bits of seed[b], counter = (index of the atom within the structure, 0, steps[b] before
+ * the increment, tag), tag 0 here and 1 in mdl_md_velocities.  From the output words w0 .. w3: u_k = (w_k + 0.5) 2^-32,
+ * xi_x, xi_y = sqrt(-2 ln u0) (cos, sin)(2 pi u1), xi_z = sqrt(-2 ln u2) cos(2 pi u3).  Nothing outside structure b enters its
+ * result: alone or in any batch it gets the same bits from the same seed.
+ * Sums by wave shuffles, then the waves through LDS in wave order; lane 0 alone reads and writes what is per structure: no atomics,
+ * bitwise repeatable.  Caller owns every buffer; no allocation, no synchronisation.  B == 0 or N == 0 returns 0 without a launch. */
+int mdl_md_step(double* pos, double* vel, const float* force, const double* mass, const uint8_t* fixed, const int64_t* node_ptr,
+                int64_t N, int64_t B, const double* dt, const double* gamma, const double* kT, const int64_t* seed,
+                const int32_t* n_steps, int32_t* steps, int32_t* status, double* ekin, double max_disp, mdlStream_t stream);
+
+/* mdl_md_velocities: Maxwell-Boltzmann velocities, vel [N, 3] fp64 written: v_i = sqrt(kT[b] / m_i) xi_i with the noise of
+ * mdl_md_step at tag 1 and step word 0; fixed atoms get 0.  zero_momentum != 0 and at least two free atoms in the structure:
+ * sum m v / sum m over the free atoms is subtracted from each of them.  Same workgroup, same sums, same repeatability. */
+int mdl_md_velocities(double* vel, const double* mass, const uint8_t* fixed, const int64_t* node_ptr, int64_t N, int64_t B,
+                      const double* kT, const int64_t* seed, int zero_momentum, mdlStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

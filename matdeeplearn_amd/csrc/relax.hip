@@ -22,38 +22,13 @@
 // The bits: contraction is off in the kernel and every fused multiply-add is written out, so the source states the arithmetic
 // (fp64 sqrt and / are correctly rounded, no fast-math flag is in the build).  A structure whose cell is frozen runs, in
 // fire_kernel<true>, the statements that are all of fire_kernel<false>: it gets the bits of mdl_fire_step because it is that code.
-#include "mdl_common.h"
+#include "struct_reduce.h"
 
 namespace mdl {
 namespace {
 
-constexpr int FIRE_THREADS = 256;
-constexpr int FIRE_WAVES = FIRE_THREADS / WAVE;
-
-// v[0 .. NSUM) summed and v[NSUM .. K) maximised over the workgroup; every lane returns with the same totals in v.
-// `red` is used once per call site (no barrier behind the read).
-template <int K, int NSUM>
-__device__ __forceinline__ void block_reduce(double* v, double (*red)[K]) {
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-        for (int off = WAVE / 2; off > 0; off >>= 1) {
-            const double o = __shfl_down(v[k], off, WAVE);
-            v[k] = k < NSUM ? v[k] + o : (o > v[k] ? o : v[k]);
-        }
-    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[wave][k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = red[0][k];
-#pragma unroll
-        for (int w = 1; w < FIRE_WAVES; ++w) t = k < NSUM ? t + red[w][k] : (red[w][k] > t ? red[w][k] : t);
-        v[k] = t;
-    }
-}
+constexpr int FIRE_THREADS = STRUCT_THREADS;                   // block_reduce (struct_reduce.h, shared with csrc/md.hip)
+constexpr int FIRE_WAVES = STRUCT_WAVES;
 
 struct FireConst {
     int32_t n_min;

@@ -26,8 +26,11 @@ Consumers of the forces: ForceField keeps the packed structures, the atom featur
 calls (the host pass above happens once), and relax moves the atoms downhill with it — one batched FIRE update per step in one
 launch (ops.fire_step, csrc/relax.hip), every structure with its own time step and its own convergence latch.  relax_cell moves
 the cell with the atoms: the same update over the atoms' rows and the three rows of the deformation gradient, driven by the strain
-gradient of energy_forces_stress (ops.fire_cell_step), still one launch per step."""
+gradient of energy_forces_stress (ops.fire_cell_step), still one launch per step.  md follows the forces at a temperature: BAOAB,
+NVE or Langevin, one launch per step too (ops.md_step, csrc/md.hip), with counter-based noise, so a structure's trajectory is the
+same alone and in any batch."""
 import collections
+import math
 
 import numpy as np
 import torch
@@ -481,3 +484,88 @@ def relax_cell(model, structs, dist_range, fmax=0.05, smax=1e-3, steps=200, rebu
     stress = _per_volume(strain, ff.cell, ff.pbc)
     smax_seen = torch.where(torch.isnan(stress).flatten(1).any(1), torch.full_like(probe.smax_seen, float("nan")), probe.smax_seen)
     return CellRelaxResult(ff.positions, ff.cell, energy, f, stress, converged, state.steps, probe.fmax_seen, smax_seen, state.done, ff.node_ptr)
+
+
+# eV, Angstrom and atomic mass units: the time unit is A sqrt(amu / eV) = 10.18 fs.  dt = 2 * EV_A_AMU.fs is two femtoseconds,
+# kT = EV_A_AMU.kB * 300 is 300 K, for a model trained on eV with masses in amu.
+Units = collections.namedtuple("Units", "fs kB")
+_E, _AMU, _K = 1.602176634e-19, 1.66053906660e-27, 1.380649e-23          # C, kg, J / K (SI 2019; CODATA 2018)
+EV_A_AMU = Units(fs=1e-15 / (1e-10 * math.sqrt(_AMU / _E)), kB=_K / _E)
+
+MDResult = collections.namedtuple("MDResult", "positions velocities energy forces ekin steps status epot_trace ekin_trace node_ptr")
+
+
+def md(model, structs, dist_range, masses, dt, steps, kT=0.0, gamma=0.0, kT_init=None, velocities=None, seed=0, fixed=None,
+       rebuild_every=1, max_disp=0.5, check_every=0, radius=8.0, max_neighbors=12, dictionary=None, output_index=None):
+    """Molecular dynamics of a batch of structures in the model's prediction: BAOAB on the forces of a ForceField, one evaluation
+    and ONE integrator launch (ops.md_step) per step, every structure with its own time step, thermostat and random stream.
+
+    model, structs, dist_range, fixed, radius, max_neighbors, dictionary, output_index   as relax; the model must be in eval()
+    masses        [N], one per atom in the order of the packed structures (tensor or array), > 0.  Units are the caller's: kT in
+                  the model's energy unit, masses and dt consistent with it (EV_A_AMU for eV, Angstrom, amu)
+    dt, kT, gamma a number or one per structure: time step > 0, thermostat temperature >= 0, friction >= 0 (1 / time).  gamma = 0
+                  is NVE: no random number is drawn, and prediction + ekin is conserved on held lists up to the integrator's
+                  O(dt^2) oscillation; gamma > 0 is Langevin dynamics at kT
+    steps         this many steps: steps + 1 evaluations, the last call of the integrator only closes the last kick
+    velocities    [N, 3] initial velocities, or None: Maxwell-Boltzmann at kT_init (None: kT) with the momentum of every structure
+                  removed (ops.md_velocities)
+    seed          an integer s (structure b is keyed s + b) or one int64 per structure.  A structure's trajectory does not depend
+                  on what else is in the batch as far as the integrator goes: its noise is counted by (atom, step)
+    rebuild_every 0: the neighbour lists of the initial positions are held throughout (the energy is one smooth function);
+                  n >= 1: the lists are rebuilt before every n-th evaluation
+    max_disp      the guard: a step that would move an atom further than this (or to a non-finite place) is not made; the
+                  structure stops at its last positions with status 2 while the others go on
+    check_every   the loop asks the device whether every structure has stopped every this many steps (the only host read besides
+                  the edge count at a rebuild, and one look at masses, dt, kT and gamma at the first step); 0: never
+
+    Returns MDResult(positions [N, 3] float64, velocities [N, 3] float64, energy [B] or [B, out] fp32 and forces [N, 3] fp32 at
+    those positions, ekin [B] float64, steps [B] int32, status [B] int32 (1 finished, 2 stopped by the guard, 0 still running:
+    only where check_every ended the loop), epot_trace [steps + 1, B(, out)] fp32 and ekin_trace [steps + 1, B] float64 — row n:
+    prediction and kinetic energy at the positions after n steps (NaN rows: evaluations not made) —, node_ptr), device tensors.
+    With ops.deterministic() two calls return the same bits."""
+    who = "md"
+    _accepted(model, dist_range)
+    if model.training:
+        raise ops.MdlError("%s: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
+                           "(and dropout makes the energy a random function)" % who)
+    steps, rebuild_every, check_every = int(steps), int(rebuild_every), int(check_every)
+    if steps < 0 or rebuild_every < 0 or check_every < 0:
+        raise ops.MdlError("%s: steps, rebuild_every and check_every must be >= 0" % who)
+    ff = ForceField(model, structs, dist_range, radius, max_neighbors, dictionary, output_index)
+    dev, N, B = ff.positions.device, ff.positions.shape[0], ff.node_ptr.numel() - 1
+
+    def per_atom(v, what, tail, dtype):
+        t = (v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v))).to(dev)
+        if tuple(t.shape) != (N,) + tail:
+            raise ops.MdlError("%s: %s must be %s with N = %d (got %s)" % (who, what, list((N,) + tail), N, tuple(t.shape)))
+        return (t != 0).to(torch.uint8) if dtype == torch.uint8 else t.to(dtype).contiguous().clone()
+
+    mass = per_atom(masses, "masses", (), torch.float64)
+    fixed = None if fixed is None else per_atom(fixed, "fixed", (), torch.uint8)
+    dt_t, kT_t, gamma_t = [_per_structure(v, B, dev, who, name) for name, v in (("dt", dt), ("kT", kT), ("gamma", gamma))]
+    if torch.is_tensor(seed) or np.ndim(seed) > 0:
+        seed_t = (seed.detach() if torch.is_tensor(seed) else torch.from_numpy(np.asarray(seed, dtype=np.int64))).to(dev, torch.int64).contiguous()
+        if tuple(seed_t.shape) != (B,):
+            raise ops.MdlError("%s: seed must be an integer or one per structure, [%d] (got %s)" % (who, B, tuple(seed_t.shape)))
+    else:
+        seed_t = torch.arange(B, dtype=torch.int64, device=dev) + int(seed)
+    if velocities is None:
+        vel = ops.md_velocities(mass, ff.node_ptr, kT_t if kT_init is None else _per_structure(kT_init, B, dev, who, "kT_init"), seed_t, fixed)
+    else:
+        vel = per_atom(velocities, "velocities", (3,), torch.float64)
+    state = ops.md_state(B, dev)
+    n_steps = torch.full((B,), steps, dtype=torch.int32, device=dev)
+    epot_trace = ekin_trace = None
+    for it in range(steps + 1):
+        if it > 0 and rebuild_every > 0 and it % rebuild_every == 0:
+            ff.rebuild()
+        energy, f = ff.evaluate()
+        ops.md_step(ff.positions, vel, f, mass, ff.node_ptr, state, dt_t, n_steps, gamma_t, kT_t, seed_t, fixed, max_disp)
+        if epot_trace is None:
+            epot_trace = torch.full((steps + 1,) + tuple(energy.shape), float("nan"), dtype=energy.dtype, device=dev)
+            ekin_trace = torch.full((steps + 1, B), float("nan"), dtype=torch.float64, device=dev)
+        epot_trace[it].copy_(energy)
+        ekin_trace[it].copy_(state.ekin)
+        if check_every > 0 and (it + 1) % check_every == 0 and bool((state.status != 0).all()):
+            break
+    return MDResult(ff.positions, vel, energy, f, state.ekin, state.steps, state.status, epot_trace, ekin_trace, ff.node_ptr)

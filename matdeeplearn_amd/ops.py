@@ -10,6 +10,7 @@ exceptions.  Every op runs a hand-written HIP kernel; there is no eager/CPU fall
 """
 import collections
 import os
+import weakref
 
 import torch
 
@@ -2922,3 +2923,150 @@ def fire_cell_step(pos, cell, vel, force, strain_grad, node_ptr, state, fmax, sm
                                    int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
                                    float(c["dt_max"]), float(c["maxstep"]), float(c["max_deform"]), stream()), "mdl_fire_cell_step")
     return state
+
+
+# ------------------------------------------------------------------------------------------------
+# Molecular dynamics: one BAOAB step of a batch of structures in one launch (csrc/md.hip)
+# ------------------------------------------------------------------------------------------------
+class MDState:
+    """Per-structure state of md_step, [B] device tensors: steps (updates made) and status (0 running, 1 finished: steps reached
+    n_steps and the last kick is closed, 2 refused: an atom would have moved further than max_disp, or to a non-finite place)
+    int32; ekin float64, the kinetic energy at the positions the forces of the last call belong to."""
+
+    __slots__ = ("steps", "status", "ekin", "_checked")
+
+    def __init__(self, steps, status, ekin):
+        self.steps, self.status, self.ekin = steps, status, ekin
+        self._checked = {}                                     # operand -> the tensor whose values md_step has read back once
+
+    def clone(self):
+        new = MDState(self.steps.clone(), self.status.clone(), self.ekin.clone())
+        new._checked = dict(self._checked)
+        return new
+
+
+def md_state(B, device=None):
+    """A fresh MDState of B structures: no step made, every structure running."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    return MDState(torch.zeros(int(B), dtype=torch.int32, device=dev), torch.zeros(int(B), dtype=torch.int32, device=dev),
+                   torch.zeros(int(B), dtype=torch.float64, device=dev))
+
+
+# per-structure operand -> (dtype, its range: ">" above zero, ">=" not below, None any value)
+_MD_PER_STRUCTURE = {"dt": (torch.float64, ">"), "gamma": (torch.float64, ">="), "kT": (torch.float64, ">="),
+                     "n_steps": (torch.int32, ">="), "seed": (torch.int64, None)}
+
+
+def _md_numbers(who, values):
+    """the range of every operand given as a plain number — before a device or the library is asked for anything"""
+    for name, v in values:
+        rng = ">" if name == "max_disp" else _MD_PER_STRUCTURE[name][1]
+        if torch.is_tensor(v) or rng is None:
+            continue
+        if not (float(v) > 0.0 if rng == ">" else float(v) >= 0.0):           # (a NaN is neither)
+            raise MdlError("%s: %s must be %s 0 (got %r)" % (who, name, rng, v))
+
+
+def _md_in_range(who, name, t, rng, checked):
+    """t > 0 (or >= 0) everywhere, read back ONCE per tensor: `checked` remembers which tensor, at which version, has passed"""
+    seen, version = checked.get(name, (None, None))
+    if rng is None or (seen is not None and seen() is t and version == t._version):
+        return
+    if not bool(((t > 0) if rng == ">" else (t >= 0)).all()):
+        raise MdlError("%s: %s must be %s 0 everywhere" % (who, name, rng))
+    checked[name] = (weakref.ref(t), t._version)
+
+
+def _md_per_structure(who, values, B, dev, checked):
+    """(name, a number or a [B] tensor) -> contiguous [B] device tensors of the operand's type; a plain seed s: s + b"""
+    out = []
+    for name, v in values:
+        dtype, rng = _MD_PER_STRUCTURE[name]
+        if torch.is_tensor(v):
+            if v.dtype != dtype or tuple(v.shape) != (B,):
+                raise MdlError("%s: %s must be a number or a [B] %s tensor with B = %d (got %s %s)" % (who, name, dtype, B, tuple(v.shape), v.dtype))
+            require_hip(v)
+            if v.device != dev:
+                raise MdlError("%s: %s must be on the device of the other tensors" % (who, name))
+            _md_in_range(who, name, v, rng, checked)
+            out.append(v.contiguous())
+        elif name == "seed":
+            out.append(torch.arange(B, dtype=torch.int64, device=dev) + int(v))
+        else:
+            out.append(torch.full((B,), v, dtype=dtype, device=dev))
+    return out
+
+
+def _md_atoms(who, mass, node_ptr, fixed, checked):
+    """the checks md_step and md_velocities share: mass [N] float64 > 0, node_ptr, fixed.  Returns (N, B, fixed as uint8 or None)"""
+    require_hip(mass, node_ptr, fixed)
+    if mass.dtype != torch.float64 or mass.dim() != 1 or not mass.is_contiguous():
+        raise MdlError("%s: mass must be a contiguous [N] float64 tensor (got %s %s)" % (who, tuple(mass.shape), mass.dtype))
+    N = mass.shape[0]
+    if node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 1:
+        raise MdlError("%s: node_ptr must be [B + 1] int64" % who)
+    if fixed is not None:
+        if fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
+            raise MdlError("%s: fixed must be [N] uint8 or bool with N = %d (got %s %s)" % (who, N, tuple(fixed.shape), fixed.dtype))
+        fixed = fixed.contiguous().view(torch.uint8)
+    if any(t.device != mass.device for t in (node_ptr, fixed) if t is not None):
+        raise MdlError("%s: mass, node_ptr and fixed must be on one device" % who)
+    _md_in_range(who, "mass", mass, ">", checked)
+    return N, node_ptr.numel() - 1, fixed
+
+
+def md_step(pos, vel, force, mass, node_ptr, state, dt, n_steps, gamma=0.0, kT=0.0, seed=0, fixed=None, max_disp=0.5):
+    """Everything between two force evaluations of a molecular-dynamics run, for every structure of a batch, in place, in ONE
+    launch: BAOAB with one force evaluation per step (the kick that closes step n and B A O A of step n + 1 are one call).
+      pos, vel [N, 3] float64 (updated in place: contiguous tensors), force [N, 3] float32 at pos, mass [N] float64 > 0, node_ptr
+      [B + 1] int64, state an MDState of B structures (updated in place), fixed [N] uint8 / bool or None (non-zero: the atom stays
+      where it is with zero velocity), max_disp > 0: a step that would move an atom further is refused as a whole (status 2,
+      positions kept to the bit).
+      Per structure, a number or a [B] tensor each: dt > 0 and gamma >= 0 (friction; 0: no thermostat, no random number), kT >= 0
+      (float64), n_steps >= 0 (int32: the call at steps == n_steps closes the last kick and sets status 1), seed (int64; a plain
+      integer s gives structure b the key s + b).
+    Call it after EVERY evaluation, n_steps + 1 times in all; state.ekin is then the kinetic energy at the evaluated positions.
+    The update, the counter layout of the noise (Philox4x32-10: a structure gets the same bits alone or in any batch) and the
+    guard are stated in include/mdl_hip.h (mdl_md_step).  No atomics: two calls from the same inputs give the same bits.  No host
+    synchronisation, except that the values of mass and of a tensor-valued dt, gamma, kT or n_steps are checked once per tensor (the
+    state remembers which it has seen).  Returns state."""
+    who = "md_step"
+    if not isinstance(state, MDState):
+        raise MdlError("%s: state must be an ops.MDState (ops.md_state)" % who)
+    per = (("dt", dt), ("gamma", gamma), ("kT", kT), ("seed", seed), ("n_steps", n_steps))
+    _md_numbers(who, per + (("max_disp", max_disp),))
+    require_hip(pos, vel, force, state.steps, state.status, state.ekin)
+    N, B, fixed = _md_atoms(who, mass, node_ptr, fixed, state._checked)
+    for name, t in (("pos", pos), ("vel", vel)):
+        if t.dtype != torch.float64 or tuple(t.shape) != (N, 3) or not t.is_contiguous():
+            raise MdlError("%s: %s must be a contiguous [N, 3] float64 tensor with N = %d (got %s %s)" % (who, name, N, tuple(t.shape), t.dtype))
+    if force.dtype != torch.float32 or tuple(force.shape) != (N, 3):
+        raise MdlError("%s: force must be [N, 3] float32 with N = %d (got %s %s)" % (who, N, tuple(force.shape), force.dtype))
+    for k, dt_ in (("steps", torch.int32), ("status", torch.int32), ("ekin", torch.float64)):
+        t = getattr(state, k)
+        if t.dtype != dt_ or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise MdlError("%s: state.%s must be a contiguous [%d] %s tensor (got %s %s)" % (who, k, B, dt_, tuple(t.shape), t.dtype))
+    if any(t.device != pos.device for t in (vel, force, mass, state.steps, state.status, state.ekin)):
+        raise MdlError("%s: pos, the other tensors and the state must be on one device" % who)
+    dt, gamma, kT, seed, n_steps = _md_per_structure(who, per, B, pos.device, state._checked)
+    check(lib().mdl_md_step(ptr(pos), ptr(vel), ptr(force.contiguous()), ptr(mass), ptr(fixed), ptr(node_ptr.contiguous()), N, B, ptr(dt),
+                            ptr(gamma), ptr(kT), ptr(seed), ptr(n_steps), ptr(state.steps), ptr(state.status), ptr(state.ekin),
+                            float(max_disp), stream()), "mdl_md_step")
+    return state
+
+
+def md_velocities(mass, node_ptr, kT, seed=0, fixed=None, zero_momentum=True):
+    """Maxwell-Boltzmann velocities [N, 3] float64 for mass [N] float64 > 0 at kT >= 0 (a number or a [B] float64 tensor): v_i =
+    sqrt(kT / m_i) xi_i from the noise of md_step (tag 1, step word 0; seed as there), fixed atoms 0.  zero_momentum: the momentum
+    of the free atoms of every structure with at least two of them is removed (the temperature of that draw is then kT (n - 1) / n
+    on average).  One launch, the same bits from the same seed whatever else is in the batch; rows outside every structure are 0."""
+    who = "md_velocities"
+    per = (("kT", kT), ("seed", seed))
+    _md_numbers(who, per)
+    checked = {}
+    N, B, fixed = _md_atoms(who, mass, node_ptr, fixed, checked)
+    kT, seed = _md_per_structure(who, per, B, mass.device, checked)
+    vel = torch.zeros((N, 3), dtype=torch.float64, device=mass.device)
+    check(lib().mdl_md_velocities(ptr(vel), ptr(mass), ptr(fixed), ptr(node_ptr.contiguous()), N, B, ptr(kT), ptr(seed),
+                                  1 if zero_momentum else 0, stream()), "mdl_md_velocities")
+    return vel
