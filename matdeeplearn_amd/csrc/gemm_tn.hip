@@ -160,11 +160,16 @@ extern "C" int mdl_gemm_tn_ex(const void* a, int64_t lda, int M, const void* y, 
     int64_t grid = cdiv(N, 128);
     if (grid > 512) grid = 512;
     if (det) grid = 1;
-    const int mt = (M + 31) / 32, ntw = ((K + 31) / 32 + 3) / 4;
+    const int ntw = ((K + 31) / 32 + 3) / 4;
+    // (instantiated for up to 4 row tiles: 128 < M <= 160 — even widths whose strides or bases kept them off the streaming kernel —
+    // takes a second launch for columns 128 .. M - 1 of A; one launch left rows 128 .. M - 1 of C unwritten)
+    for (int m0 = 0; m0 < M; m0 += 128) {
+        const int mm = (M - m0 < 128) ? M - m0 : 128, mt = (mm + 31) / 32;
 #define MDL_TN(MT_, NTW_) hipLaunchKernelGGL((gemm_tn_kernel<MT_, NTW_>), dim3((unsigned)grid), dim3(256), 0, st, \
-        (const bf16_t*)a, (int)lda, M, (const bf16_t*)b, (int)ldb, K, c, N)
-    if (ntw == 1) { if (mt == 1) MDL_TN(1, 1); else if (mt == 2) MDL_TN(2, 1); else if (mt == 3) MDL_TN(3, 1); else MDL_TN(4, 1); }
-    else { if (mt == 1) MDL_TN(1, 2); else if (mt == 2) MDL_TN(2, 2); else if (mt == 3) MDL_TN(3, 2); else MDL_TN(4, 2); }
+        (const bf16_t*)a + m0, (int)lda, mm, (const bf16_t*)b, (int)ldb, K, c + (int64_t)m0 * K, N)
+        if (ntw == 1) { if (mt == 1) MDL_TN(1, 1); else if (mt == 2) MDL_TN(2, 1); else if (mt == 3) MDL_TN(3, 1); else MDL_TN(4, 1); }
+        else { if (mt == 1) MDL_TN(1, 2); else if (mt == 2) MDL_TN(2, 2); else if (mt == 3) MDL_TN(3, 2); else MDL_TN(4, 2); }
 #undef MDL_TN
+    }
     return check_launch("mdl_gemm_tn");
 }
