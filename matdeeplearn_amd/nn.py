@@ -111,8 +111,8 @@ def _lin(lin, h, act=None, in_act=None, out_pre=False, pre=None):
 def _seq(seq, h, pre=None, dist=None):
     """Sequential of Linear / activation modules; a Linear followed by ShiftedSoftplus / ReLU runs as ONE fused dense layer.
     Between two fused layers of the chain the intermediate tensor is private to this function, so the activation derivative
-    is handed down the chain (ops._LinearActTN: the later layer's backward returns the gradient w.r.t. the earlier layer's
-    pre-activation, the earlier layer's backward reads neither its output nor applies a derivative).
+    is handed down the chain (ops._LinearActTN, in_act / out_pre of ops._linear_backward: the later layer's backward returns the
+    gradient w.r.t. the earlier layer's pre-activation, the earlier layer's backward reads neither its output nor applies a derivative).
     pre: the outputs of the chain's Linear layers, already formed by a fused forward (CFConv: ops.cfconv_fused) — every layer
     must then take the fused dense path, whose autograd node only records the graph.
     dist = (d_norm [E] fp32, offsets [G], coeff): h is rbf_expand(d_norm), detached.  When d_norm requires a gradient the first
@@ -143,10 +143,10 @@ def _seq(seq, h, pre=None, dist=None):
         nxt = layers[j + 1] if j + 1 < len(layers) else None
         fused = h.dtype != m.weight.dtype and ops.linear_act_fused_ok(h, m.weight, act)
         # hand this layer's derivative to the next one: both fused, this one activated, the next one a Linear on our output
+        # (our output has the rows, dtype and layout of h, so of ops.linear_act_fused_ok only the shape window is left to ask)
         give = (fused and act in ("relu", "ssp") and nxt is not None and nxt[1] is not False and torch.is_grad_enabled()
                 and nxt[0].weight.requires_grad and nxt[0].in_features == m.out_features
-                and ops._hip_shape_ok(nxt[0].out_features, nxt[0].in_features)
-                and (nxt[1] != "ssp" or nxt[0].out_features % 2 == 0) and h.shape[0] >= ops._DENSE_MIN_ROWS)
+                and ops._fused_fwd_shape_ok(nxt[0].out_features, nxt[0].in_features, nxt[1]))
         prev_act = layers[j - 1][1] if handed else None
         if want_dd and j == 0:
             assert pre is None

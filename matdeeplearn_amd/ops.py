@@ -1545,53 +1545,113 @@ def nnconv_msg(Y, h, csr, out_channels):
 # library handles badly (47 us for a 64 x 64 x 8192 product, 0.7 ms for 64 x 114 x 2e5)
 # ------------------------------------------------------------------------------------------------
 _TN_COLSUM = True
+_DENSE_BWD_WIDE = True   # ... also when both widths exceed 128 (SchNet's 150 x 150 filter layer)
+_DENSE_BWD = True     # dX + dW + db of a tall dense layer in one pass (csrc/dense_bwd.hip)
 
 
-class _LinearTN(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, w_lp=None, b_lp=None):
-        # w_lp / b_lp: the caller's copies of weight / bias already in x.dtype (one multi-tensor cast per step instead of
-        # two launches per layer); gradients go to the fp32 masters
-        w = weight.to(x.dtype) if w_lp is None else w_lp
-        b = None if bias is None else (bias.to(x.dtype) if b_lp is None else b_lp)
-        out = torch.nn.functional.linear(x, w, b)
-        ctx.save_for_backward(x, w)
-        ctx.wdtype, ctx.has_bias, ctx.shape = weight.dtype, bias is not None, tuple(weight.shape)
-        return out
+# --- what the kernels admit, each window stated once: shapes alone (tests/test_dense_budget_host.py sweeps them), then operands ---
+def _hip_shape_ok(M, K):
+    """(out, in) features the streaming dense kernels take: linear.hip forward and gemm_tn.hip weight gradient."""
+    return 1 <= M <= 160 and 4 <= K <= 256 and K % 2 == 0 and (M <= 128 or (K <= 160 and M % 2 == 0))
 
-    @staticmethod
-    def backward(ctx, g):
-        x, w = ctx.saved_tensors
-        if _dense_bwd_ok(ctx, g, x, w):
-            return _dense_bwd(ctx, g, x, w) + (None, None)
-        dx, dw, db = _linear_tn_grads(ctx, g.contiguous(), x, w)
-        return dx, dw, db, None, None
+
+def _fused_fwd_shape_ok(M, K, act):
+    """the fused forward GEMM + bias + activation (_LinearActTN) takes an [M, K] layer followed by `act`"""
+    # (ssp: the one-pass softplus backward works on element PAIRS — an odd width would reach it with an odd element count)
+    return act in ("relu", "ssp", None) and _hip_shape_ok(M, K) and (act != "ssp" or M % 2 == 0)
+
+
+def _dense_bwd_shape_ok(M, K, has_bias, wide=True):
+    """mdl_dense_bwd takes an [M, K] layer: even widths in [34, 160], the bias sums in column K; wide: also both sides above 128"""
+    kb = K + (1 if has_bias else 0)
+    return 34 <= min(M, K) and M <= 160 and kb <= 160 and M % 2 == 0 and K % 2 == 0 and (wide or not (M > 128 and kb > 128))
+
+
+def _relu_bn_shape_ok(M, K, has_bias, tables=0):
+    """_LinearReluBN: the one-pass backward's shapes (never both above 128), M % 4, at most three tables and M <= 128 with them"""
+    return _dense_bwd_shape_ok(M, K, has_bias, wide=False) and M % 4 == 0 and tables <= 3 and (M <= 128 or not tables)
+
+
+def _tn_colsum_shape_ok(M, K):
+    """the streaming TN kernel forms column sums (db) / stages an activation: even widths, the ones column K inside the fifth tile"""
+    return 1 <= M <= 160 and M % 2 == 0 and K % 2 == 0 and K <= 158
+
+
+def _dword_rows(t):
+    """rows of 2-byte elements the kernels address as dwords: unit column stride, even row stride, base on a dword"""
+    return t.stride(1) == 1 and t.stride(0) % 2 == 0 and t.data_ptr() % 4 == 0
 
 
 def _tn_split_ok(x, weight):
-    """dW of a Linear with 256 < in <= 512 as two TN-GEMM halves (_linear_tn_grads): even widths, dword-aligned halves"""
+    """dW of a Linear with 256 < in <= 512 as two TN-GEMM halves (_tn_plan): even widths, dword-aligned halves"""
     M, K = weight.shape
     kh = (K // 2 + 1) & ~1
-    return (K <= 512 and K % 2 == 0 and M % 2 == 0 and M <= 128 and x.stride(0) % 2 == 0 and x.data_ptr() % 4 == 0
-            and kh <= 256 and K - kh <= 256)
+    return K <= 512 and K % 2 == 0 and M % 2 == 0 and M <= 128 and _dword_rows(x) and kh <= 256 and K - kh <= 256
 
 
 def _tn_wide_out_ok(x, weight):
     """dW of a Linear with MANY outputs and few inputs (the GRU's 3C x C gate matrices, mpnn.py:160-161) as TN GEMMs of the
-    TRANSPOSED product: dW^T[K, M] = x^T g in column chunks of <= 150 outputs (_linear_tn_grads)"""
+    TRANSPOSED product: dW^T[K, M] = x^T g in column chunks of <= 150 outputs (_tn_plan)"""
     M, K = weight.shape
-    return (160 < M <= 600 and M % 2 == 0 and 4 <= K <= 160 and K % 2 == 0 and x.stride(0) % 2 == 0 and x.data_ptr() % 4 == 0)
+    return 160 < M <= 600 and M % 2 == 0 and 4 <= K <= 160 and K % 2 == 0 and _dword_rows(x)
 
 
-def _hip_shape_ok(M, K):
-    """(out, in) features the streaming dense kernels take: linear.hip forward and gemm_tn.hip weight gradient."""
-    return 1 <= M <= 160 and 4 <= K <= 256 and K % 2 == 0 and (M <= 128 or (K <= 160 and M % 2 == 0))
+def _linear_tn_ok(x, weight):
+    """the launches of _tn_plan form the weight gradient of this layer (ops.linear)"""
+    M, K = weight.shape
+    return (M <= 128 or _hip_shape_ok(M, K) or _tn_wide_out_ok(x, weight)) and (K <= 256 or _tn_split_ok(x, weight))
 
 
 def _dx_hip_ok(g, w):
     M, K = w.shape
     return (g.dtype == torch.bfloat16 and g.is_cuda and g.shape[0] >= _DENSE_MIN_ROWS and g.is_contiguous() and g.data_ptr() % 16 == 0
             and _hip_shape_ok(K, M) and M % 2 == 0)
+
+
+def _dense_bwd_ok(ctx, g, x, w, y=None):
+    """mdl_dense_bwd takes this layer's backward: the input gradient is wanted, its shape window, dword-addressable bf16 rows."""
+    return (_DENSE_BWD and ctx.needs_input_grad[0] and g.is_cuda and g.shape[0] >= _DENSE_MIN_ROWS and w.is_contiguous()
+            and _dense_bwd_shape_ok(*ctx.shape, ctx.has_bias, _DENSE_BWD_WIDE) and g.dtype == x.dtype == w.dtype == torch.bfloat16
+            and _dword_rows(g) and _dword_rows(x) and (y is None or (y.dtype == torch.bfloat16 and _dword_rows(y))))
+
+
+def _tn_act_ok(ctx, g, x, y, w=None):
+    """The activation derivative can go into the staging of the backward products instead of a pass of its own: the TN
+    GEMM (dW, db) always, the dX product when it runs on the streaming kernel (or is not wanted)."""
+    M, K = ctx.shape
+    if ctx.needs_input_grad[0] and not (w is not None and g.is_contiguous() and y.is_contiguous() and _dx_hip_ok(g, w)):
+        return False
+    return (_TN_COLSUM and _hip_shape_ok(M, K) and _tn_colsum_shape_ok(M, K) and g.dtype == torch.bfloat16
+            and _dword_rows(g) and _dword_rows(x) and _dword_rows(y))
+
+
+def _lowp_pair(lowp, x):
+    """the step's low-precision copies (weight, bias) of a layer if they are in x.dtype, else (None, None)"""
+    return lowp if lowp is not None and lowp[0].dtype == x.dtype else (None, None)
+
+
+def _wb(x, weight, bias, w_lp=None, b_lp=None):
+    """(w, b) in x.dtype from the fp32 masters, or the caller's copies w_lp / b_lp already in x.dtype (one multi-tensor cast per
+    step instead of two launches per layer).  Called inside a node's forward: no autograd, the gradients go to the masters."""
+    b = None if bias is None else (bias.to(x.dtype) if b_lp is None else b_lp)
+    return (weight.to(x.dtype) if w_lp is None else w_lp), b
+
+
+def _dw_db_zeros(M, K, device, db=True):
+    """fp32 zeros for dW (flat, M * K) | db [M] out of the step's gradient arena (one fill per step)"""
+    buf = _zeros_grad(M * K + (M if db else 0), device)
+    return buf[:M * K], buf[M * K:]
+
+
+def _table_args(idx, tables):
+    """K6's three (table, index) pointer slots, and the dense tables behind them (to be held until the launch is enqueued)"""
+    tabs = [None if t is None else t.contiguous() for t in tables] + [None] * (3 - len(tables))
+    return [ptr(v) for slot in zip(tabs, list(idx) + [None] * (3 - len(idx))) for v in slot], tabs
+
+
+def _table_grads(g, idx, rows, needs):
+    """the gathered tables' gradients: segment sums of the layer's gradient rows g (needs is never set for an absent table)"""
+    return tuple(scatter(g, ix, 0, r, "sum") if need else None for ix, r, need in zip(idx, rows, needs))
 
 
 def _dx_hip(g, w, act_y=None):
@@ -1614,118 +1674,120 @@ def _dx_hip(g, w, act_y=None):
     return g @ w
 
 
-_DENSE_BWD_WIDE = True   # ... also when both widths exceed 128 (SchNet's 150 x 150 filter layer)
-_DENSE_BWD = True     # dX + dW + db of a tall dense layer in one pass (csrc/dense_bwd.hip)
-
-
-def _dense_bwd_ok(ctx, g, x, w, y=None):
-    """mdl_dense_bwd takes this layer's backward: the input gradient is wanted, even widths in [34, 160], dword-addressable
-    rows."""
-    M, K = ctx.shape
-    kb = K + (1 if ctx.has_bias else 0)
-    return (_DENSE_BWD and ctx.needs_input_grad[0] and g.dtype == torch.bfloat16 and g.is_cuda and g.shape[0] >= _DENSE_MIN_ROWS
-            and 34 <= M <= 160 and 34 <= K and kb <= 160 and M % 2 == 0 and K % 2 == 0 and (_DENSE_BWD_WIDE or not (M > 128 and kb > 128))
-            and g.stride(1) == 1 and x.stride(1) == 1 and g.stride(0) % 2 == 0 and x.stride(0) % 2 == 0
-            and g.data_ptr() % 4 == 0 and x.data_ptr() % 4 == 0 and w.is_contiguous() and w.dtype == torch.bfloat16
-            and x.dtype == torch.bfloat16
-            and (y is None or (y.dtype == torch.bfloat16 and y.stride(1) == 1 and y.stride(0) % 2 == 0 and y.data_ptr() % 4 == 0)))
-
-
 def _dense_bwd(ctx, g, x, w, act_y=None, xout=0, want_gm=False):
     """(dx, dW, db[, g']) of y = act(x W^T + b) from ONE pass over g, y, x (callers check _dense_bwd_ok); act_y = (code, y):
     g is the gradient w.r.t. the activated output; xout: x is the relu (1) / shifted-softplus (2) output of a private layer in
     front and dx is returned w.r.t. that layer's pre-activation; want_gm: also return g' = g .* act'(y) (bf16, dense)."""
     M, K = ctx.shape
     N = g.shape[0]
-    buf = _zeros_grad(M * K + M, g.device)
-    dw, dbv = buf[:M * K].view(M, K), buf[M * K:]
+    dw, dbv = _dw_db_zeros(M, K, g.device)
     dx = torch.empty((N, K), dtype=g.dtype, device=g.device)
     gm = torch.empty((N, M), dtype=g.dtype, device=g.device) if want_gm else None
     code, y = act_y if act_y is not None else (0, None)
     check(lib().mdl_dense_bwd_ex(ptr(g), g.stride(0), M, ptr(y), 0 if y is None else y.stride(0), code, ptr(x), x.stride(0), K,
                                  ptr(w), ptr(dx), K, xout, ptr(gm), ptr(dw), ptr(dbv) if ctx.has_bias else None,
                                  ptr(_tn_scratch(g.device, N)), N, dtype_code(g) | _dflag(), stream()), "mdl_dense_bwd")
-    out = (dx, dw.to(ctx.wdtype), dbv.to(ctx.wdtype) if ctx.has_bias else None)
+    out = (dx, dw.view(M, K).to(ctx.wdtype), dbv.to(ctx.wdtype) if ctx.has_bias else None)
     return out + (gm,) if want_gm else out
 
 
-def _tn_act_ok(ctx, g, x, y, w=None):
-    """The activation derivative can go into the staging of the backward products instead of a pass of its own: the TN
-    GEMM (dW, db) always, the dX product when it runs on the streaming kernel (or is not wanted)."""
+def _tn_plan(M, K, has_bias, ldg, ldx):
+    """The TN-GEMM launches that form dW (and db) of an [M, K] layer from g [N, M] (row stride ldg; an odd M is padded first) and
+    x [N, K] (row stride ldx), one (kernel M, kernel K, lda, ldb, column sums, lo, hi) per launch:
+      M > 160   many outputs, few inputs: dW^T = x^T g[:, lo:hi], one launch per chunk of <= 150 gradient columns (the library
+                runs the (M x N)(N x K) form of this N ~ 6e4 contraction at 234 us for 300 x 100; this is 2 x ~15 us)
+      K > 256   wide inputs (MEGNet's node block: [x | v_e | u[batch]] = 3d columns): the kernel takes <= 256 input columns, so
+                two products over the column halves x[:, lo:hi] (the library: 335 us for 100 x 300 x 1e5, on 9 workgroups)
+      else      one launch over x[:, 0:K]
+    column sums: db out of the same pass (the sums of g ride in a padding column of the B tile and are flushed with one gathered
+    atomic instruction per block) where the layer has a bias and the kernel-level shape allows; else the library's reduction."""
+    if M > 160:
+        nch = -(-M // 150)
+        mc = ((M + nch - 1) // nch + 1) & ~1
+        return [(K, min(m0 + mc, M) - m0, ldx, ldg, False, m0, min(m0 + mc, M)) for m0 in range(0, M, mc)]
+    if K > 256:
+        kh = (K // 2 + 1) & ~1
+        return [(M, kh, ldg, ldx, has_bias and _tn_colsum_shape_ok(M, kh), 0, kh), (M, K - kh, ldg, ldx, False, kh, K)]
+    return [(M, K, ldg, ldx, has_bias and _tn_colsum_shape_ok(M, K), 0, K)]
+
+
+def _tn_dw_db(ctx, g, x, act_y=None):
+    """(dW, db) of y = x W^T + b in the masters' dtype from the launches of _tn_plan, accumulated in fp32.  act_y = (code, y):
+    g is the gradient w.r.t. the ACTIVATED output y and the derivative is applied inside the TN GEMM's staging (callers check
+    _tn_act_ok).  db out of the same pass needs dword-addressable operands too; ops.configure(tn_colsum=False) turns it off."""
     M, K = ctx.shape
-    if ctx.needs_input_grad[0] and not (w is not None and g.is_contiguous() and y.is_contiguous() and _dx_hip_ok(g, w)):
-        return False
-    return (_TN_COLSUM and M % 2 == 0 and K % 2 == 0 and K <= 158 and (M <= 128 or K <= 160)
-            and g.dtype == torch.bfloat16 and x.stride(0) % 2 == 0 and g.stride(0) % 2 == 0 and y.stride(0) % 2 == 0
-            and x.data_ptr() % 4 == 0 and g.data_ptr() % 4 == 0 and y.data_ptr() % 4 == 0 and g.stride(1) == 1
-            and y.stride(1) == 1)
+    code, y = act_y if act_y is not None else (0, None)
+    # the streaming kernel stages rows as dwords: pad an odd width (the model's 1-column output layer) with a zero column
+    ga = torch.nn.functional.pad(g, (0, 1)) if M % 2 else g
+    Ma = ga.shape[1]
+    plan = _tn_plan(Ma, K, ctx.has_bias, ga.stride(0), x.stride(0))
+    fused_db = plan[0][4] and _TN_COLSUM and _dword_rows(ga) and _dword_rows(x)
+    transposed = Ma > 160
+    flat, dbv = _dw_db_zeros(Ma, K, g.device, db=not transposed)
+    parts, off = [], 0
+    for Mk, Kk, lda, ldb, colsum, lo, hi in plan:
+        parts.append(flat[off:off + Mk * Kk].view(Mk, Kk))
+        off += Mk * Kk
+        a, b = (x, ga[:, lo:hi]) if transposed else (ga, x[:, lo:hi] if lo else x)              # (lo = 0: the same base address)
+        check(_gemm_tn(a, lda, Mk, y, 0 if y is None else y.stride(0), code, b, ldb, Kk, parts[-1], dbv if colsum and fused_db else None,
+                       g.shape[0], dtype_code(g) | _dflag(), g.device), "mdl_gemm_tn_act" if code else "mdl_gemm_tn_colsum")
+    dw = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+    dw = dw.t() if transposed else dw[:M]
+    db = (dbv[:M] if fused_db else g.sum(dim=0, dtype=torch.float32)).to(ctx.wdtype) if ctx.has_bias else None
+    return dw.to(ctx.wdtype), db
 
 
 def _linear_tn_grads(ctx, g, x, w, act_y=None):
-    """(dx, dW, db) of y = x W^T + b for a tall x: streaming HIP product (or library GEMM) for dx, one TN-GEMM launch for dW
-    and db.  act_y = (code, y): g is the gradient w.r.t. the ACTIVATED output y, dx is not wanted (_tn_act_ok), and the
-    activation derivative is applied inside the TN GEMM's staging (mdl_gemm_tn_act)."""
-    M, K = ctx.shape
-    if act_y is not None:
-        buf = _zeros_grad(M * K + M, g.device)
-        dw, dbv = buf[:M * K].view(M, K), buf[M * K:]
-        check(_gemm_tn(g, g.stride(0), M, act_y[1], act_y[1].stride(0), act_y[0], x, x.stride(0), K, dw,
-                       dbv if ctx.has_bias else None, g.shape[0], dtype_code(g) | _dflag(), g.device), "mdl_gemm_tn_act")
-        dx = _dx_hip(g, w, act_y) if ctx.needs_input_grad[0] else None
-        return dx, dw.to(ctx.wdtype), (dbv.to(ctx.wdtype) if ctx.has_bias else None)
-    dx = _dx_hip(g, w) if ctx.needs_input_grad[0] else None
-    if M > 160:
-        # many outputs, few inputs: the transposed product dW^T = x^T g, one TN GEMM per chunk of <= 150 gradient columns
-        # (the library runs the (M x N)(N x K) form of this N ~ 6e4 contraction at 234 us for 300 x 100; this is 2 x ~15 us)
-        nch = -(-M // 150)
-        mc = ((M + nch - 1) // nch + 1) & ~1
-        buf = _zeros_grad(K * M, g.device)
-        parts, off = [], 0
-        for m0 in range(0, M, mc):
-            m1 = min(m0 + mc, M)
-            c = buf[off:off + K * (m1 - m0)].view(K, m1 - m0)
-            off += K * (m1 - m0)
-            gs = g[:, m0:m1]
-            check(_gemm_tn(x, x.stride(0), K, None, 0, 0, gs, g.stride(0), m1 - m0, c, None, g.shape[0], dtype_code(g) | _dflag(), g.device),
-                  "mdl_gemm_tn_colsum")
-            parts.append(c)
-        dw = torch.cat(parts, dim=1).t()
-        db = g.sum(dim=0, dtype=torch.float32).to(ctx.wdtype) if ctx.has_bias else None
-        return dx, dw.to(ctx.wdtype), db
-    if K > 256:
-        # wide inputs (MEGNet's node block: [x | v_e | u[batch]] = 3d columns): the TN GEMM takes <= 256 input columns, so dW
-        # is two products over column halves of x (the library's (M x N)(N x K) form runs this K = N ~ 1e5 contraction on 9
-        # workgroups: 335 us for 100 x 300 x 1e5)
-        kh = (K // 2 + 1) & ~1
-        buf = _zeros_grad(M * K + M, g.device)
-        d1, d2, dbv = buf[:M * kh].view(M, kh), buf[M * kh:M * K].view(M, K - kh), buf[M * K:]
-        fused_db = ctx.has_bias and kh <= 158
-        check(_gemm_tn(g, g.stride(0), M, None, 0, 0, x, x.stride(0), kh, d1, dbv if fused_db else None, g.shape[0],
-                       dtype_code(g) | _dflag(), g.device), "mdl_gemm_tn_colsum")
-        x2 = x[:, kh:]
-        check(_gemm_tn(g, g.stride(0), M, None, 0, 0, x2, x.stride(0), K - kh, d2, None, g.shape[0], dtype_code(g) | _dflag(), g.device),
-              "mdl_gemm_tn_colsum")
-        dw = torch.cat([d1, d2], dim=1)
-        db = None
-        if ctx.has_bias:
-            db = dbv.to(ctx.wdtype) if fused_db else g.sum(dim=0, dtype=torch.float32).to(ctx.wdtype)
-        return dx, dw.to(ctx.wdtype), db
-    ga, Ma = g, M
-    if M % 2:                               # the streaming kernel stages rows as dwords: pad an odd width (the model's
-        ga, Ma = torch.nn.functional.pad(g, (0, 1)), M + 1             # 1-column output layer) with a zero column
-    # db out of the same pass (mdl_gemm_tn_colsum: the column sums of g ride in a padding column of the B tile and are
-    # flushed with one gathered atomic instruction per block); ops.configure(tn_colsum=False) falls back to the library reduction
-    fused_db = (_TN_COLSUM and ctx.has_bias and K % 2 == 0 and K <= 158 and x.stride(0) % 2 == 0
-                and ga.stride(0) % 2 == 0 and x.data_ptr() % 4 == 0 and ga.data_ptr() % 4 == 0)
-    buf = _zeros_grad(Ma * K + Ma, g.device)                                       # dW | db: zero-filled (one fill per step)
-    dw, dbv = buf[:Ma * K].view(Ma, K), buf[Ma * K:]
-    check(_gemm_tn(ga, ga.stride(0), Ma, None, 0, 0, x, x.stride(0), K, dw, dbv if fused_db else None, g.shape[0],
-                   dtype_code(g) | _dflag(), g.device), "mdl_gemm_tn_colsum")
-    dw = dw[:M]
-    db = None
-    if ctx.has_bias:                          # bias gradient = column sums of g: out of the same pass when the shape allows
-        db = dbv[:M].to(ctx.wdtype) if fused_db else g.sum(dim=0, dtype=torch.float32).to(ctx.wdtype)
-    return dx, dw.to(ctx.wdtype), db
+    """(dx, dW, db) of y = x W^T + b for a tall x: streaming HIP product (or library GEMM) for dx, _tn_dw_db for dW and db.
+    act_y = (code, y): both apply the derivative of the ACTIVATED output y in their staging (_tn_act_ok), the TN GEMM first."""
+    staged = _tn_dw_db(ctx, g, x, act_y) if act_y is not None else None
+    dx = _dx_hip(g, w, act_y) if ctx.needs_input_grad[0] else None
+    return (dx,) + (staged or _tn_dw_db(ctx, g, x))
+
+
+def _linear_backward(ctx, g, x, w, code, out, in_act, want_masked_rows, stage_act=True):
+    """(dx, dW, db, rows) of out = act(x W^T + b) for every dense node: THE place where the backward's route is chosen.
+    code: the activation whose derivative g still lacks (0: none, or g already is w.r.t. the pre-activation), out: the saved
+    activated output; in_act: x is the relu (1) / ssp (2) output of a private layer in front and dx is returned w.r.t. that
+    layer's pre-activation (nn._seq's hand-over); want_masked_rows: also return rows = g .* act'(out), dense (K6's tables).
+      1. one pass over g, out, x for everything, the hand-over in its epilogue (_dense_bwd_ok)
+      2. the derivative in the staging of the TN GEMM and of the streaming dX (_tn_act_ok; stage_act=False: K6 never took it)
+      3. the masked gradient materialised (library mask / mdl_ssp_bwd), then _linear_tn_grads; behind 2. and 3. the hand-over"""
+    act_y = (code, out) if code else None
+    if _dense_bwd_ok(ctx, g, x, w, out if code else None):
+        res = _dense_bwd(ctx, g, x, w, act_y, xout=in_act, want_gm=bool(want_masked_rows and code))
+        return res if len(res) > 3 else res + (g.contiguous() if want_masked_rows else None,)
+    if code and stage_act and not want_masked_rows and _tn_act_ok(ctx, g, x, out, w):
+        dx, dw, db = _linear_tn_grads(ctx, g, x, w, act_y)
+    else:
+        if code == 1:
+            g = torch.ops.aten.threshold_backward(g, out, 0)
+        elif code == 2:                            # d/dv (softplus(v) - ln2) = sigmoid(v) = 1 - exp(-(out + ln2))
+            g = g.contiguous()
+            dpre = torch.empty_like(g)
+            check(lib().mdl_ssp_bwd(ptr(g), ptr(out), ptr(dpre), g.numel(), dtype_code(g), stream()), "mdl_ssp_bwd")
+            g = dpre
+        g = g.contiguous()
+        dx, dw, db = _linear_tn_grads(ctx, g, x, w)
+    if dx is not None and in_act:                  # the hand-over on the paths without the fused epilogue
+        dx = (torch.ops.aten.threshold_backward(dx, x, 0) if in_act == 1 else
+              (dx.float() * (1.0 - torch.exp(-(x.float() + _LN2)))).to(dx.dtype))
+    return dx, dw, db, (g if want_masked_rows else None)
+
+
+class _LinearTN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, w_lp=None, b_lp=None):
+        w, b = _wb(x, weight, bias, w_lp, b_lp)
+        out = torch.nn.functional.linear(x, w, b)
+        ctx.save_for_backward(x, w)
+        ctx.wdtype, ctx.has_bias, ctx.shape = weight.dtype, bias is not None, tuple(weight.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        return _linear_backward(ctx, g, x, w, 0, None, 0, False)[:3] + (None, None)
 
 
 _MLP_HEAD = True        # post-FC head (post_lin_list + lin_out) as one launch per direction
@@ -1744,8 +1806,7 @@ class _LinearActTN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, w_lp, b_lp, act, in_act=0, out_pre=False, pre=None):
         # pre: this layer's output, already formed by a fused forward (cfconv_fused) — the node then only records the graph
-        w = weight.to(x.dtype) if w_lp is None else w_lp
-        b = None if bias is None else (bias.to(x.dtype) if b_lp is None else b_lp)
+        w, b = _wb(x, weight, bias, w_lp, b_lp)
         N, K = x.shape
         M = weight.shape[0]
         if pre is not None:
@@ -1763,26 +1824,7 @@ class _LinearActTN(torch.autograd.Function):
     def backward(ctx, g):
         x, w, out = ctx.saved_tensors
         code = 0 if ctx.out_pre else _ACT_CODE.get(ctx.act, 0)
-        tail = (None, None, None, None, None, None)
-        if _dense_bwd_ok(ctx, g, x, w, out if code else None):
-            return _dense_bwd(ctx, g, x, w, (code, out) if code else None, xout=ctx.in_act) + tail
-        if code and _tn_act_ok(ctx, g, x, out, w):
-            dx, dw, db = _linear_tn_grads(ctx, g, x, w, act_y=(code, out))
-        else:
-            if code == 1:
-                g = torch.ops.aten.threshold_backward(g, out, 0)
-            elif code == 2:                            # d/dv (softplus(v) - ln2) = sigmoid(v) = 1 - exp(-(out + ln2))
-                g = g.contiguous()
-                dpre = torch.empty_like(g)
-                check(lib().mdl_ssp_bwd(ptr(g), ptr(out), ptr(dpre), g.numel(), dtype_code(g), stream()), "mdl_ssp_bwd")
-                g = dpre
-            dx, dw, db = _linear_tn_grads(ctx, g.contiguous(), x, w)
-        if dx is not None and ctx.in_act:              # the hand-over on the paths without the fused epilogue
-            if ctx.in_act == 1:
-                dx = torch.ops.aten.threshold_backward(dx, x, 0)
-            else:
-                dx = (dx.float() * (1.0 - torch.exp(-(x.float() + _LN2)))).to(dx.dtype)
-        return (dx, dw, db) + tail
+        return _linear_backward(ctx, g, x, w, code, out, ctx.in_act, False)[:3] + (None,) * 6
 
 
 class _LinearGatherAct(torch.autograd.Function):
@@ -1791,41 +1833,25 @@ class _LinearGatherAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, act, idx, *tables):
-        w = weight.to(x.dtype)
-        b = None if bias is None else bias.to(x.dtype)
+        w, b = _wb(x, weight, bias)
         N, K = x.shape
         M = weight.shape[0]
-        tabs = [None if t is None else t.contiguous() for t in tables]
-        tabs += [None] * (3 - len(tabs))
-        ids = list(idx) + [None] * (3 - len(idx))
+        targs, tabs = _table_args(idx, tables)
         out = torch.empty((N, M), dtype=x.dtype, device=x.device)
         check(_launch_timed("edge_linear", lambda: lib().mdl_linear_gather_act(
-            ptr(x), ptr(w), ptr(b), ptr(tabs[0]), ptr(ids[0]), ptr(tabs[1]), ptr(ids[1]), ptr(tabs[2]), ptr(ids[2]), ptr(out),
-            N, K, M, 1 if act == "relu" else 0, dtype_code(x), stream())), "mdl_linear_gather_act")
+            ptr(x), ptr(w), ptr(b), *targs, ptr(out), N, K, M, 1 if act == "relu" else 0, dtype_code(x), stream())),
+            "mdl_linear_gather_act")
         ctx.save_for_backward(x, w, out if act == "relu" else None)
-        ctx.idx, ctx.rows = ids, [None if t is None else t.shape[0] for t in tabs]
-        ctx.wdtype, ctx.has_bias, ctx.shape, ctx.act, ctx.ntab = weight.dtype, bias is not None, tuple(weight.shape), act, len(tables)
+        ctx.idx, ctx.rows = list(idx), [None if t is None else t.shape[0] for t in tabs]
+        ctx.wdtype, ctx.has_bias, ctx.shape, ctx.act = weight.dtype, bias is not None, tuple(weight.shape), act
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, w, out = ctx.saved_tensors
-        if _dense_bwd_ok(ctx, g, x, w, out if ctx.act == "relu" else None):
-            # one pass: dX, dW, db and the masked gradient rows the table gradients are segment sums of
-            need_gm = any(ctx.needs_input_grad[5 + t] and ctx.rows[t] is not None for t in range(ctx.ntab))
-            res = _dense_bwd(ctx, g, x, w, (1, out) if ctx.act == "relu" else None, want_gm=need_gm and ctx.act == "relu")
-            dx, dw, db = res[:3]
-            g = res[3] if len(res) > 3 else g.contiguous()
-        else:
-            if ctx.act == "relu":
-                g = torch.ops.aten.threshold_backward(g, out, 0)
-            g = g.contiguous()
-            dx, dw, db = _linear_tn_grads(ctx, g, x, w)
-        dts = []
-        for t in range(ctx.ntab):
-            need = ctx.needs_input_grad[5 + t] and ctx.rows[t] is not None
-            dts.append(scatter(g, ctx.idx[t], 0, ctx.rows[t], "sum") if need else None)
-        return (dx, dw, db, None, None) + tuple(dts)
+        needs = ctx.needs_input_grad[5:]
+        dx, dw, db, rows = _linear_backward(ctx, g, x, w, 1 if ctx.act == "relu" else 0, out, 0, any(needs), stage_act=False)
+        return (dx, dw, db, None, None) + _table_grads(rows, ctx.idx, ctx.rows, needs)
 
 
 def linear_gather_act(x, weight, bias, act, gathered):
@@ -1855,9 +1881,9 @@ class _MlpHead(torch.autograd.Function):
     def forward(ctx, x, lowp, f32_out, *params):
         import ctypes
         NL = len(params) // 2
-        ws = [(params[2 * l].to(x.dtype) if lowp is None or lowp[l] is None else lowp[l][0]).contiguous() for l in range(NL)]
-        bs = [None if params[2 * l + 1] is None else
-              (params[2 * l + 1].to(x.dtype) if lowp is None or lowp[l] is None else lowp[l][1]) for l in range(NL)]
+        wb = [_wb(x, params[2 * l], params[2 * l + 1], *((None, None) if lowp is None or lowp[l] is None else lowp[l]))
+              for l in range(NL)]
+        ws, bs = [w.contiguous() for w, _ in wb], [b for _, b in wb]
         N, K0 = x.shape
         M = [int(w.shape[0]) for w in ws]
         # f32_out: the prediction as fp32 rows (the values the bf16 output holds) — the model's `out.float()` behind the head and
@@ -1887,9 +1913,9 @@ class _MlpHead(torch.autograd.Function):
         Ks = [K0] + M[:-1]
         dws, dbs = [], []
         for l in range(NL):
-            buf = _zeros_grad(M[l] * Ks[l] + M[l], x.device)
-            dws.append(buf[:M[l] * Ks[l]].view(M[l], Ks[l]))
-            dbs.append(buf[M[l] * Ks[l]:] if ctx.has_bias[l] else None)
+            flat, dbv = _dw_db_zeros(M[l], Ks[l], x.device)
+            dws.append(flat.view(M[l], Ks[l]))
+            dbs.append(dbv if ctx.has_bias[l] else None)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         Ma = (ctypes.c_int * NL)(*M)
         check(lib().mdl_mlp_head_bwd(ptr(x), _ptr_array(ws), _ptr_array(hs + [None]), ptr(gy), ptr(dx), _ptr_array(dws), _ptr_array(dbs),
@@ -1958,11 +1984,8 @@ def matmul_wide(x, w):
 
 def linear_act_fused_ok(x, weight, act):
     """the fused dense layer (_LinearActTN) takes (x, weight, act)"""
-    # (ssp: the one-pass softplus backward works on element PAIRS — an odd width would reach it with an odd element count)
-    return (act in ("relu", "ssp", None) and x.dtype == torch.bfloat16 and x.is_cuda and x.dim() == 2 and x.is_contiguous()
-            and x.shape[0] >= _DENSE_MIN_ROWS and _hip_shape_ok(weight.shape[0], weight.shape[1])
-            and (act != "ssp" or weight.shape[0] % 2 == 0)
-            and x.data_ptr() % 16 == 0 and weight.requires_grad)
+    return (x.dtype == torch.bfloat16 and x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.shape[0] >= _DENSE_MIN_ROWS
+            and _fused_fwd_shape_ok(weight.shape[0], weight.shape[1], act) and x.data_ptr() % 16 == 0 and weight.requires_grad)
 
 
 def linear_act(x, weight, bias, act, lowp=None, in_act=None, out_pre=False, pre=None):
@@ -1971,8 +1994,7 @@ def linear_act(x, weight, bias, act, lowp=None, in_act=None, out_pre=False, pre=
     in_act / out_pre: the activation hand-over of a private chain (see _LinearActTN; callers check linear_act_fused_ok for
     both layers first)."""
     if linear_act_fused_ok(x, weight, act):
-        w_lp, b_lp = (lowp if lowp is not None and lowp[0].dtype == x.dtype else (None, None))
-        return _LinearActTN.apply(x, weight, bias, w_lp, b_lp, act, _ACT_CODE.get(in_act, 0), out_pre, pre)
+        return _LinearActTN.apply(x, weight, bias, *_lowp_pair(lowp, x), act, _ACT_CODE.get(in_act, 0), out_pre, pre)
     assert not in_act and not out_pre and pre is None, "linear_act: activation hand-over on a layer that is not fused"
     y = linear(x, weight, bias, lowp)
     if act is None:
@@ -2073,10 +2095,7 @@ def rbf_linear_act(edge_attr, weight, bias, act, dist, lowp=None, out_pre=False,
         y = linear_act(edge_attr, weight, bias, act, lowp, None, out_pre, None)
     if not ok:
         return y
-    if lowp is not None and lowp[0].dtype == y.dtype:
-        w = lowp[0].detach()
-    else:
-        w = weight.detach().to(y.dtype)
+    w = _wb(y, weight.detach(), None, _lowp_pair(lowp, y)[0])[0].detach()
     return _LinearDist.apply(y, w.contiguous(), d_norm, offsets.float().contiguous(), float(coeff), act == "relu" and not out_pre)
 
 
@@ -2154,11 +2173,8 @@ def linear(x, weight, bias, lowp=None):
     """F.linear in the dtype of x (fp32 master weights); bf16 inputs with many rows, out <= 128, in <= 256 take the
     HIP TN GEMM for dW, anything else the library autograd path.  `lowp` = (weight, bias) already cast to x.dtype."""
     if (x.dtype == torch.bfloat16 and x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= _DENSE_MIN_ROWS
-            and (weight.shape[0] <= 128 or _hip_shape_ok(weight.shape[0], weight.shape[1]) or _tn_wide_out_ok(x, weight))
-            and (weight.shape[1] <= 256 or _tn_split_ok(x, weight)) and weight.requires_grad):
-        if lowp is not None and lowp[0].dtype == x.dtype:
-            return _LinearTN.apply(x, weight, bias, lowp[0], lowp[1])
-        return _LinearTN.apply(x, weight, bias)
+            and _linear_tn_ok(x, weight) and weight.requires_grad):
+        return _LinearTN.apply(x, weight, bias, *_lowp_pair(lowp, x))
     return torch.nn.functional.linear(x, weight.to(x.dtype), None if bias is None else bias.to(x.dtype))
 
 
@@ -2489,15 +2505,12 @@ class _LinearReluBN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, w_lp, b_lp, bn_w, bn_b, rm, rv, eps, momentum, idx, *tables):
-        w = weight.to(x.dtype) if w_lp is None else w_lp
-        b = None if bias is None else (bias.to(x.dtype) if b_lp is None else b_lp)
+        w, b = _wb(x, weight, bias, w_lp, b_lp)
         N, K = x.shape
         M = weight.shape[0]
         dt = dtype_code(x)
         y = torch.empty((N, M), dtype=x.dtype, device=x.device)
-        tabs = [None if t is None else t.contiguous() for t in tables]
-        tb = tabs + [None] * (3 - len(tabs))
-        ids = list(idx) + [None] * (3 - len(idx))
+        targs, tabs = _table_args(idx, tables)
         R = lib().mdl_bn_sums_rows()
         buf = _zeros_step((R + 3, M), x.device)                       # sums | the epilogue's shift row | save
         sums, save = buf[:R], buf[R + 1:]
@@ -2505,17 +2518,15 @@ class _LinearReluBN(torch.autograd.Function):
         # the statistics of the BatchNorm ride in the dense layer's epilogue (per-column sums of the rounded outputs about output
         # row 0, which the kernel evaluates for itself and leaves in the shift row) —
         # except in deterministic mode, where the one-workgroup statistics kernel gives the run-to-run reproducible sums
-        in_epilogue = not _DET and len(tabs) in (0, 2) and K <= 160
+        in_epilogue = not _DET and len(tables) in (0, 2) and K <= 160
         if in_epilogue:
-            launch = lambda: lib().mdl_linear_act_stats(
-                ptr(x), ptr(w), ptr(b), ptr(tb[0]), ptr(ids[0]), ptr(tb[1]), ptr(ids[1]), ptr(tb[2]), ptr(ids[2]), ptr(y),
-                N, K, M, 1, ptr(sums), ptr(nd), dt, stream())
+            launch = lambda: lib().mdl_linear_act_stats(ptr(x), ptr(w), ptr(b), *targs, ptr(y), N, K, M, 1, ptr(sums), ptr(nd), dt,
+                                                        stream())
             # (bench.py's K6 events: the edge block's first layer only — the launches with gathered tables)
-            check(_launch_timed("edge_linear", launch) if tabs else launch(), "mdl_linear_act_stats")
-        elif tabs:
+            check(_launch_timed("edge_linear", launch) if tables else launch(), "mdl_linear_act_stats")
+        elif tables:
             check(_launch_timed("edge_linear", lambda: lib().mdl_linear_gather_act(
-                ptr(x), ptr(w), ptr(b), ptr(tb[0]), ptr(ids[0]), ptr(tb[1]), ptr(ids[1]), ptr(tb[2]), ptr(ids[2]), ptr(y),
-                N, K, M, 1, dt, stream())), "mdl_linear_gather_act")
+                ptr(x), ptr(w), ptr(b), *targs, ptr(y), N, K, M, 1, dt, stream())), "mdl_linear_gather_act")
         else:
             check(lib().mdl_linear_act(ptr(x), ptr(w), ptr(b), ptr(y), N, K, M, 1, dt, stream()), "mdl_linear_act")
         gw, gb = _f32c(bn_w), _f32c(bn_b)
@@ -2526,7 +2537,7 @@ class _LinearReluBN(torch.autograd.Function):
                                    float(momentum), ptr(nd), dt | (_lib.MDL_BN_SHIFT_ROW if in_epilogue else 0), stream()),
               "mdl_bn_apply")
         ctx.save_for_backward(x, w, y, save, gw)
-        ctx.n_dev, ctx.idx, ctx.rows, ctx.ntab = nd, list(idx), [None if t is None else t.shape[0] for t in tabs], len(tabs)
+        ctx.n_dev, ctx.idx, ctx.rows = nd, list(idx), [None if t is None else t.shape[0] for t in tabs]
         ctx.wdtype, ctx.has_bias, ctx.shape = weight.dtype, bias is not None, tuple(weight.shape)
         ctx.bn_has = (bn_w is not None, bn_b is not None)
         ctx.bn_wdt = None if bn_w is None else bn_w.dtype
@@ -2535,8 +2546,7 @@ class _LinearReluBN(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gz):
         x, w, y, save, gw = ctx.saved_tensors
-        M, K = ctx.shape
-        N = x.shape[0]
+        N, M = y.shape
         gz = gz.contiguous()
         dt = dtype_code(x)
         R = lib().mdl_bn_sums_rows()
@@ -2548,38 +2558,25 @@ class _LinearReluBN(torch.autograd.Function):
                                             stream()), "mdl_bn_bwd_apply_relu")
         dgamma = sums[R - 1].to(ctx.bn_wdt) if ctx.bn_has[0] else None
         dbeta = sums[R - 2].to(ctx.bn_wdt) if ctx.bn_has[1] else None
-        buf = _zeros_grad(M * K + M, x.device)
-        dw, dbv = buf[:M * K].view(M, K), buf[M * K:]
-        dx = torch.empty((N, K), dtype=x.dtype, device=x.device)
-        check(lib().mdl_dense_bwd_ex(ptr(gp), M, M, None, 0, 0, ptr(x), x.stride(0), K, ptr(w), ptr(dx), K, 0, None, ptr(dw),
-                                     ptr(dbv) if ctx.has_bias else None, ptr(_tn_scratch(x.device, N)), N, dt | _dflag(), stream()),
-              "mdl_dense_bwd")
-        dts = []
-        for t in range(ctx.ntab):
-            need = ctx.needs_input_grad[12 + t] and ctx.rows[t] is not None
-            dts.append(scatter(gp, ctx.idx[t], 0, ctx.rows[t], "sum") if need else None)
-        return (dx if ctx.needs_input_grad[0] else None, dw.to(ctx.wdtype), dbv.to(ctx.wdtype) if ctx.has_bias else None,
-                None, None, dgamma, dbeta, None, None, None, None, None) + tuple(dts)
+        dx, dw, db, _ = _linear_backward(ctx, gp, x, w, 0, None, 0, False)      # (gp is w.r.t. the pre-activation: no activation left)
+        return (dx, dw, db, None, None, dgamma, dbeta) + (None,) * 5 + _table_grads(gp, ctx.idx, ctx.rows, ctx.needs_input_grad[12:])
 
 
 def linear_relu_bn_ok(x, weight, has_bias, gathered=None):
     """The fused Linear -> ReLU -> BatchNorm1d(train) node takes this layer: bf16 rows with a gradient, the dense-backward
     shapes (even widths in [34, 160], not both above 128), at most three gathered tables."""
     M, K = weight.shape
-    kb = K + (1 if has_bias else 0)
     return (_DENSE_BWD and x.dtype == torch.bfloat16 and x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.shape[0] >= _DENSE_MIN_ROWS
             and x.requires_grad and torch.is_grad_enabled() and weight.requires_grad
-            and 34 <= M <= (128 if gathered else 160) and 34 <= K and kb <= 160 and M % 2 == 0 and K % 2 == 0
-            and not (M > 128 and kb > 128) and M % 4 == 0 and x.data_ptr() % 16 == 0 and (gathered is None or len(gathered) <= 3))
+            and _relu_bn_shape_ok(M, K, has_bias, len(gathered or ())) and x.data_ptr() % 16 == 0)
 
 
 def linear_relu_bn(x, weight, bias, lowp, bn_weight, bn_bias, running_mean, running_var, eps, momentum, gathered=None):
     """BatchNorm1d(relu(F.linear(x, weight, bias) + sum_i table_i[index_i])) with batch statistics (callers check
     linear_relu_bn_ok); `gathered` = [(table [rows, M], index [N] int), ...]."""
-    w_lp, b_lp = (lowp if lowp is not None and lowp[0].dtype == x.dtype else (None, None))
     gathered = gathered or []
     idx = [ix if ix.dtype == torch.int32 else ix.to(torch.int32) for _, ix in gathered]
-    return _LinearReluBN.apply(x, weight, bias, w_lp, b_lp, bn_weight, bn_bias, running_mean, running_var, eps, momentum, idx,
+    return _LinearReluBN.apply(x, weight, bias, *_lowp_pair(lowp, x), bn_weight, bn_bias, running_mean, running_var, eps, momentum, idx,
                                *[t.to(x.dtype) for t, _ in gathered])
 
 

@@ -455,7 +455,8 @@ def mutated(name, mutation):
 # ---------------------------------------------------------------------------------------------
 LAYER_N = 130
 # name -> (M, K, act, input gradient wanted, the launches expected).  A launch is ("dense", ldg, M, ldx, K, act, db) for
-# mdl_dense_bwd_ex or ("tn", lda, M, ldb, K, act, colsum, byte offset of B's base past 16-byte alignment) for ops._gemm_tn.
+# mdl_dense_bwd_ex or ("tn", lda, M, ldb, K, act, colsum, byte offset of B's base past 16-byte alignment) for ops._gemm_tn
+# (the launches of ops._tn_plan, made by ops._tn_dw_db; the route is chosen in ops._linear_backward).
 LAYER_CASES = {
     "dense_relu": (66, 50, "relu", True, [("dense", 66, 66, 50, 50, 1, True)]),                  # ops._dense_bwd
     "dense_ssp": (130, 94, "ssp", True, [("dense", 130, 130, 94, 94, 2, True)]),

@@ -194,7 +194,7 @@ def test_layer_cases_are_what_their_names_say(name):
         ref = c["ref"][k]
         assert c["model"][k].shape == ref.shape
         assert float((c["model"][k].double() - ref).abs().max()) <= 2e-2 * float(ref.abs().max()), (name, k)
-    # the launches, from the arithmetic of ops._linear_tn_grads restated
+    # the launches, from the arithmetic of ops._tn_plan restated
     if K > 256:
         kh = (K // 2 + 1) & ~1
         assert [(c_[3], c_[4], c_[6], c_[7]) for c_ in calls] == [(K, kh, kh <= 158, 0), (K, K - kh, False, (2 * kh) % 16)]
@@ -215,3 +215,86 @@ def test_layer_cases_are_what_their_names_say(name):
             assert B.tn_route(c_[2], c_[4], c_[6], c_[5], c_[1], c_[3], 0, 0, B.LAYER_N)[0] == S
         else:
             assert B.dense_route(c_[2], c_[4], c_[6], c_[5], B.LAYER_N)[0] == "dx"
+
+
+# ---------------------------------------------------------------------------------------------
+# the admission windows of matdeeplearn_amd/ops.py against the mirrors of the launchers: what the host layer admits, the kernels take
+# ---------------------------------------------------------------------------------------------
+class _Rows:
+    """what the shape predicates read of an operand: dense rows on a dword"""
+
+    def __init__(self, rows, cols):
+        self.shape = (rows, cols)
+
+    def stride(self, d):
+        return self.shape[1] if d == 0 else 1
+
+    def data_ptr(self):
+        return 0
+
+
+def _inside(fn, *a):
+    """the route, or None where the mirror's assertion of the launcher's domain fails"""
+    try:
+        return fn(*a)
+    except AssertionError:
+        return None
+
+
+def test_one_pass_window_lies_inside_the_kernels():
+    """Every shape the one-pass dense backward is given lies inside the window mdl_dense_bwd_ex asserts, with every activation
+    code; the Linear -> ReLU -> BatchNorm node asks for nothing the one-pass window does not hold."""
+    from matdeeplearn_amd import ops
+    admitted, bad = 0, []
+    for M in range(1, 200):
+        for K in range(1, 300):
+            for bias in (False, True):
+                one_pass = ops._dense_bwd_shape_ok(M, K, bias)
+                assert one_pass or not ops._dense_bwd_shape_ok(M, K, bias, wide=False)
+                if one_pass:
+                    admitted += 1
+                    bad += [(M, K, bias, act) for act in (0, 1, 2) if _inside(B.dense_route, M, K, bias, act, B.LAYER_N) is None]
+                for tables in range(5):
+                    if ops._relu_bn_shape_ok(M, K, bias, tables):
+                        assert ops._dense_bwd_shape_ok(M, K, bias, wide=False) and tables <= 3, (M, K, bias, tables)
+    assert admitted == 8128 and not bad, (admitted, bad[:10])
+
+
+def test_staged_activation_window_lands_on_the_streaming_kernel():
+    """Where the fused forward and the column-sum / staged-activation window both admit a layer, the TN GEMM with the activation
+    staged (and with the column sums, for a bias) is the streaming kernel: never refused, never the scalar-load fallback."""
+    from matdeeplearn_amd import ops
+    admitted, bad = 0, []
+    for M in range(1, 200):
+        for K in range(1, 300):
+            for act, code in ((None, 0), ("relu", 1), ("ssp", 2)):
+                if not (ops._fused_fwd_shape_ok(M, K, act) and ops._tn_colsum_shape_ok(M, K)):
+                    continue
+                for bias in (False, True):
+                    admitted += 1
+                    r = _inside(B.tn_route, M, K, bias, code, M, K, 0, 0, B.LAYER_N)
+                    if r is None or r[0] != S:
+                        bad.append((M, K, act, bias, r))
+    assert admitted > 10000 and not bad, (admitted, bad[:10])
+
+
+def test_every_launch_of_the_weight_gradient_plan_is_taken():
+    """For every layer ops.linear admits (ops._linear_tn_ok: up to 600 outputs as transposed chunks, up to 512 inputs as column
+    halves), every TN launch of ops._tn_plan — the plan ops._tn_dw_db itself walks — lies inside the domain mdl_gemm_tn_ex asserts,
+    and a launch that carries column sums lands on the streaming kernel (the fallback refuses them)."""
+    from matdeeplearn_amd import ops
+    admitted, launches, bad = 0, 0, []
+    for M in range(1, 602):
+        for K in range(1, 514):
+            if not ops._linear_tn_ok(_Rows(B.LAYER_N, K), _Rows(M, K)):
+                continue
+            admitted += 1
+            Ma = M + M % 2                                                    # (an odd width is padded with a zero column)
+            for bias in (False, True):
+                for Mk, Kk, lda, ldb, colsum, lo, hi in ops._tn_plan(Ma, K, bias, Ma, K):
+                    launches += 1
+                    assert hi - lo == Kk, (M, K)                              # (the B operand is the column slice lo:hi)
+                    r = _inside(B.tn_route, Mk, Kk, colsum, 0, lda, ldb, 0, (2 * lo) % 4, B.LAYER_N)
+                    if r is None or r[0] not in ((S,) if colsum else (S, F)):
+                        bad.append((M, K, bias, (Mk, Kk, lda, ldb, colsum, lo, hi), r))
+    assert admitted > 40000 and launches > 2 * admitted and not bad, (admitted, launches, bad[:10])
