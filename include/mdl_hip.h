@@ -55,8 +55,8 @@ enum {
  *                      HIP-vs-HIP regression checks (graph replay vs eager, padded rows, data-parallel exchange).
  *   MDL_K3_PER_WAVE /  MdlCgConv.flags of mdl_cgconv_bwd_ex with bf16 by-source sums: force the per-wave kernel / the
  *   MDL_K3_EDGE_LANE   edge-per-lane kernel 2 instead of the edge-count heuristic (kernel 2 from 4e5 edges).
- *   MDL_BN_SHIFT_ROW   mdl_bn_apply_n only: the sums were formed by the PRODUCER of the rows (mdl_linear_act_stats,
- *                      mdl_cgconv_fwd_ex) about the per-column shift it stored behind the totals rows of the sums buffer
+ *   MDL_BN_SHIFT_ROW   mdl_bn_apply_n only: the sums were formed by the PRODUCER of the rows (mdl_linear_act_stats)
+ *                      about the per-column shift it stored behind the totals rows of the sums buffer
  *                      (row 2 MDL_BN_REPLICAS + 2), instead of about the first row as mdl_bn_stats forms them.
  *   MDL_SPLIT_BF16     CGConv kernels with MDL_F32 storage (MdlCgConv.flags of mdl_cgconv_fwd_ex / mdl_cgconv_bwd_ex; OR-ed
  *                      into `dtype` for mdl_cgconv_wpack_bytes / mdl_cgconv_pack_weights[_multi], whose packed layout it
@@ -157,7 +157,7 @@ int mdl_cgconv_fwd(const void* x, const void* edge_attr, const int32_t* rowptr, 
                    void* out, int64_t N, int64_t E, int C, int G, int aggr, int dtype, mdlStream_t stream);
 
 /* ---- CGConv, struct entry points (round 5) ------------------------------------------------------------------------------
- * The forward with its optional epilogue, the backward edge pass and the node kernel each take ONE argument struct: every
+ * The forward, the backward edge pass and the node kernel each take ONE argument struct: every
  * variant the positional entry points of rounds 1-4 had grown (`_bwd`, `_bwd_h`, `_bwd_hb`, `_bwd_node`, `_bwd_node_z`,
  * `_bwd_node_h`) is a field here, and the execution flags have a field of their own instead of riding in `dtype`.
  * `size` must be sizeof(the struct): a caller built against another layout is rejected (MDL_E_ARG), never misread; fields
@@ -179,15 +179,6 @@ typedef struct MdlCgConv {
     const float* bpack;
     /* forward (mdl_cgconv_fwd_ex) */
     void* out;                /* [N, C] */
-    float* bn_sums;           /* optional: statistics of `out` for the training-mode BatchNorm1d behind the layer
-                               * (cgcnn.py:143), formed in the epilogue — per column sum (v - shift) and sum (v - shift)^2 of the
-                               * ROUNDED outputs over the rows that exist, into one of the MDL_BN_REPLICAS copies (layout of
-                               * mdl_bn_stats, caller zero-fills, (2 MDL_BN_REPLICAS + 3) * C floats: the kernel stores the shift
-                               * it used in the row behind the totals rows); follow with
-                               * mdl_bn_apply_n(..., dtype | MDL_BN_SHIFT_ROW).  bf16, C in {32, 64}, G = 50, no eperm. */
-    const float* bn_shift;    /* [C] fp32 or NULL (zeros): any per-column value near the column mean, e.g. the beta of the
-                               * BatchNorm in front of the layer — keeps E[v^2] - E[v]^2 from cancelling in fp32 */
-    const int64_t* bn_rows;   /* device row count of a padded static batch, or NULL (N) */
     /* backward edge pass (mdl_cgconv_bwd_ex).  With dpre_k = d loss / d (W z_k + b) in R^{2Cp} (f half | s half):
      *     r_tgt[i, :] = sum_{k: tgt_k = i} dpre_k      [N, 2Cp] in `dtype`, written once per node (no atomics)
      *     r_src[j, :] += sum_{k: src_k = j} dpre_k     [N, 2Cp] in r_src_dtype, atomics; caller zero-fills
@@ -200,9 +191,6 @@ typedef struct MdlCgConv {
     void* r_src;
     int32_t r_src_dtype;      /* MDL_F32; or MDL_BF16 (dtype MDL_BF16, C in {32, 64, 128}, G = 50, no eperm): packed bf16 atomics,
                                * half the atomic operations and bytes; what the balance prefix and the MDL_K3_* flags go with */
-    int32_t ld_dwe;           /* leading dimension of dwe in floats; 0 = Gp.  With ld_dwe = 2C + G and dwe = dW + 2C the rows land
-                               * straight in the two Linears' stacked weight gradient dW [2C, 2C + G] (rows f | s, columns target |
-                               * source | edge; C == Cp) and mdl_cgconv_assemble_grads is not needed */
     float* dwe;
     float* db;
     void* workspace;          /* optional scratch, mdl_cgconv_workspace_bytes (dynamic group scheduling of the per-wave kernel) */
@@ -239,9 +227,6 @@ typedef struct MdlCgNode {
     int64_t N;
     int32_t C;
     int32_t r_src_dtype;      /* MDL_F32 | MDL_BF16: what the edge pass accumulated */
-    int32_t ld_dwn;           /* 0: dwn is [4Cp, C] as above.  > 0: dwn IS the stacked weight gradient dW [2C, ld_dwn] of the two Linears
-                               * (ld_dwn = 2C + G): block b of the product's rows is added to rows (b & 1) C + c, columns (b >> 1) C + k */
-    int32_t reserved;
     const void* x;            /* [N, C] */
     const void* grad_out;     /* [N, C] */
     const void* r_tgt;        /* [N, 2Cp] in dtype */

@@ -121,8 +121,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, 
     for (int u = 0; u < U; ++u) V::ld(x + (min(q0 + u * stride, total - 1) / CG) * C + cg * W, v[u]);
     float mean[W], scale[W], shiftv[W], sh[W];
     V::ld(x + cg * W, sh);
-    if (shift_row) {                                          // MDL_BN_SHIFT_ROW: the producer of the sums (mdl_linear_act_stats,
-        const float* srow = sums + (size_t)(2 * BN_R + 2) * C;   // mdl_cgconv_fwd_ex) left its shift behind the totals rows
+    if (shift_row) {                                          // MDL_BN_SHIFT_ROW: the producer of the sums (mdl_linear_act_stats)
+        const float* srow = sums + (size_t)(2 * BN_R + 2) * C;   // left its shift behind the totals rows
 #pragma unroll
         for (int j = 0; j < W; ++j) sh[j] = srow[cg * W + j];
     }

@@ -239,7 +239,6 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
     const bool x3 = (p.flags & MDL_SPLIT_BF16) != 0;
     const CgDims d = cg_dims(p.C, p.G, dtype, x3);
     p.Cp = d.Cp; p.KE = d.KE; p.KT = d.KT; p.WS = d.WS; p.EKS = d.EKS; p.NS = d.NS; p.GP = d.GP;
-    if (p.ldwe > 0) p.GP = p.ldwe;      // dwe rows straight into the caller's [2C, 2C + G] weight-gradient matrix (MdlCgConv.ld_dwe)
     p.w_elems = 2 * d.Cp * d.WS;
     const bool wsp = p.pt != nullptr;  // W-split entry points: packed weights = edge-feature part only
     if (wsp) { p.WS = d.EKS; p.w_elems = 2 * d.Cp * d.EKS; }
@@ -261,8 +260,7 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
 
     const int et_bytes = (32 * d.EKS * (int)sizeof(T) + 15) & ~15;
     // e tile, tgt-slot bytes, source ids, src-slot bytes, bitmap, one-hot tables (32 + 32 + 64 rows)
-    p.wave_lds_bytes = et_bytes + 32 + 128 + 32 + 16 + ((bwd && sizeof(T) == 2) ? 128 * OHS * 2 + 64 + 256 : 0) +
-                       ((!bwd && p.bn_sums) ? 2 * d.Cp * 4 : 0);      // forward with BatchNorm statistics: the wave's [2][Cp] running sums
+    p.wave_lds_bytes = et_bytes + 32 + 128 + 32 + 16 + ((bwd && sizeof(T) == 2) ? 128 * OHS * 2 + 64 + 256 : 0);
     const int w_bytes = (p.w_elems * (int)sizeof(T) + 15) & ~15;
     // MDL_DETERMINISTIC (backward): ONE wave per channel slice walks the whole batch — every sum this kernel forms with atomics
     // (r_src rows, dwe, db) then receives its terms from a single wave in program order, i.e. the same bits on every run.
@@ -395,19 +393,6 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
 
 #endif
 
-    if constexpr (sizeof(T) == 2) {
-        if (!bwd && p.bn_sums) {       // forward with the BatchNorm statistics in its epilogue: the static all-slices kernel only
-            if (!(fast && all_slices && w_lds)) { set_error("%s: BatchNorm statistics need the static bf16 kernels", name); return MDL_E_UNSUPP; }
-            auto kf = d.Cp == 64 ? cgconv_fwd_kernel<T, 64, 50, 9, 2, 1, false, 0, true> : cgconv_fwd_kernel<T, 32, 50, 9, 2, 1, false, 0, true>;
-            hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(kf), lds);
-            if (e != hipSuccess) { set_error("%s: LDS attribute (%d B): %s", name, lds, hipGetErrorString(e)); return MDL_E_LAUNCH; }
-            hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(waves * 64), lds, st, p);
-            return check_launch(name);
-        }
-    } else if (!bwd && p.bn_sums) {
-        set_error("%s: BatchNorm statistics are bf16 only", name);
-        return MDL_E_UNSUPP;
-    }
 #define MDL_CG_LAUNCH(CP_, G_, VEC_, EW_, WM_)                                                               \
     do {                                                                                                     \
         auto kf = bwd ? cgconv_bwd_kernel<T, CP_, G_, VEC_, EW_, WM_> : cgconv_fwd_kernel<T, CP_, G_, VEC_, EW_, WM_>; \
@@ -479,7 +464,7 @@ static int cg_launch(bool bwd, CgParams& p, int dtype, hipStream_t st, const cha
                     e = set_max_dynamic_lds(reinterpret_cast<const void*>(kf), lds);                                          \
                     if (e == hipSuccess) hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(waves * 64), lds, st, p);          \
                 } else {                                                                                                      \
-                    auto kf = cgconv_fwd_kernel<T, CP_, 50, 9, 1, 1, false, 0, false, true>;                                  \
+                    auto kf = cgconv_fwd_kernel<T, CP_, 50, 9, 1, 1, false, 0, true>;                                         \
                     e = set_max_dynamic_lds(reinterpret_cast<const void*>(kf), lds);                                          \
                     if (e == hipSuccess) hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(waves * 64), lds, st, p);          \
                 }                                                                                                             \
@@ -647,16 +632,12 @@ extern "C" int mdl_cgconv_fwd(const void* x, const void* edge_attr, const int32_
     return cg_launch<float>(false, p, dtype, (hipStream_t)stream, "mdl_cgconv_fwd");
 }
 
-static int cg_fwd_stats_ok(int C, int G, int dtype) {      // the static all-slices forward: the kernel that has the epilogue
-    return (dtype == MDL_BF16 && G == 50 && (C == 32 || C == 64)) ? 1 : 0;
-}
-
 extern "C" int mdl_cgconv_fwd_ex(const MdlCgConv* a, mdlStream_t stream) {
     using namespace mdl;
     MDL_REQUIRE(a && a->size == sizeof(MdlCgConv), MDL_E_ARG, "mdl_cgconv_fwd_ex: argument struct of another layout (size %u, expected %u)",
                 a ? a->size : 0u, (unsigned)sizeof(MdlCgConv));
     MDL_REQUIRE((a->flags & ~(uint32_t)(MDL_DETERMINISTIC | MDL_SPLIT_BF16)) == 0, MDL_E_ARG, "mdl_cgconv_fwd_ex: unknown flag bits %#x", a->flags);
-    MDL_REQUIRE(!(a->flags & MDL_SPLIT_BF16) || (a->dtype == MDL_F32 && !a->bn_sums), MDL_E_UNSUPP, "mdl_cgconv_fwd_ex: MDL_SPLIT_BF16 goes with MDL_F32 storage");
+    MDL_REQUIRE(!(a->flags & MDL_SPLIT_BF16) || a->dtype == MDL_F32, MDL_E_UNSUPP, "mdl_cgconv_fwd_ex: MDL_SPLIT_BF16 goes with MDL_F32 storage");
     int rc = cg_check("mdl_cgconv_fwd_ex", a->x, a->edge_attr, a->rowptr, a->src, a->tgt, a->wpack, a->bpack, a->N, a->E, a->C, a->G,
                       a->aggr, a->dtype);
     if (rc) return rc;
@@ -665,15 +646,6 @@ extern "C" int mdl_cgconv_fwd_ex(const MdlCgConv* a, mdlStream_t stream) {
     p.x = a->x; p.ea = a->edge_attr; p.rowptr = a->rowptr; p.src = a->src; p.tgt = a->tgt; p.eperm = a->eperm;
     p.wpack = a->wpack; p.bpack = a->bpack; p.out = a->out; p.N = a->N; p.E = a->E; p.C = a->C; p.G = a->G; p.aggr = a->aggr;
     p.flags = (int)(a->flags & MDL_SPLIT_BF16);
-    if (a->bn_sums) {
-        // BatchNorm statistics in the epilogue: the static all-slices kernel only (bf16, C in {32, 64}, G = 50, CSR-ordered edge features)
-        MDL_REQUIRE(cg_fwd_stats_ok(a->C, a->G, a->dtype) && !a->eperm && a->E > 0 &&
-                        reinterpret_cast<uintptr_t>(a->x) % 16 == 0 && reinterpret_cast<uintptr_t>(a->out) % 16 == 0 &&
-                        reinterpret_cast<uintptr_t>(a->edge_attr) % 4 == 0,
-                    MDL_E_UNSUPP, "mdl_cgconv_fwd_ex: BatchNorm statistics need bf16, C in {32, 64}, G = 50, edge features in CSR order, "
-                                  "16-byte aligned x / out (C=%d G=%d dtype=%d)", a->C, a->G, a->dtype);
-        p.bn_sums = a->bn_sums; p.bn_shift = a->bn_shift; p.bn_nrows = a->bn_rows;
-    }
     if (a->dtype == MDL_BF16) return cg_launch<bf16_t>(false, p, a->dtype, (hipStream_t)stream, "mdl_cgconv_fwd_ex");
     return cg_launch<float>(false, p, a->dtype, (hipStream_t)stream, "mdl_cgconv_fwd_ex");
 }
@@ -840,8 +812,6 @@ extern "C" int mdl_cgconv_bwd_ex(const MdlCgConv* a, mdlStream_t stream) {
     p.wpack = a->wpack; p.bpack = a->bpack; p.gout = a->grad_out; p.r_tgt = a->r_tgt; p.r_src = static_cast<float*>(a->r_src);
     p.dwe = a->dwe; p.db = a->db;
     p.N = a->N; p.E = a->E; p.C = a->C; p.G = a->G; p.aggr = a->aggr;
-    MDL_REQUIRE(a->ld_dwe == 0 || a->ld_dwe >= a->G, MDL_E_ARG, "mdl_cgconv_bwd_ex: ld_dwe (%d) below G", a->ld_dwe);
-    p.ldwe = a->ld_dwe;
     // optional caller workspace: work counters for dynamic group scheduling (zeroed here, on the stream)
     p.ctr = (a->workspace && a->workspace_bytes >= mdl_cgconv_workspace_bytes(a->N, a->E, a->C, a->G, dtype))
                 ? static_cast<unsigned*>(a->workspace) : nullptr;

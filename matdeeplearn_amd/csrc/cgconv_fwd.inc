@@ -9,9 +9,7 @@ constexpr int FWD_WAVES = 2;       // waves per SIMD it is register-allocated fo
 constexpr int FWD_WAVES_F32 = 1;
 constexpr int FWD_PRE_DEPTH = 3;   // all-slices forward: pinned LDS-read / MFMA interleave in pre_tile, reads issued ahead (-6 %)
 constexpr int FWD_AGE_SKEW = 60;   // all-slices forward at two workgroups per CU: per mille of extra work for the older half
-// BN_: the instantiation whose epilogue also forms the BatchNorm statistics of the output (p.bn_sums) — a variant of its own, so
-// that the plain forward keeps its register allocation (it sits at 252 of 256 VGPRs)
-template <typename T, int CP_, int G_, int VEC, int EW, int WM, bool AB_ = false, int WSP = 0, bool BN_ = false, bool X3 = false>   // WM: 0 global, 1 LDS; X3: split-bf16 products on fp32 storage
+template <typename T, int CP_, int G_, int VEC, int EW, int WM, bool AB_ = false, int WSP = 0, bool X3 = false>   // WM: 0 global, 1 LDS; X3: split-bf16 products on fp32 storage
 __global__ __launch_bounds__(FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? FWD_WAVES_F32 : FWD_WAVES)) void cgconv_fwd_kernel(CgParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef Mma<T> M;
@@ -65,46 +63,6 @@ __global__ __launch_bounds__(FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? FWD_WA
                 R.nb = gwu == nw_total - 1 ? (int)p.N : wave_lower_bound(p.rowptr, (int)p.N, cut(gwu + 1), lane);
             }
         }
-        // BatchNorm statistics of the output (p.bn_sums).  The forward has no register to spare across its tile loop (252 VGPRs
-        // at two waves per SIMD), so the running sums live in the wave's LDS region ([2][CP_] floats behind the staging
-        // buffers, zeroed by setup_wave): a group's epilogue adds its rows' contributions, the wave's exit turns them into two
-        // atomics per channel on one of the MDL_BN_REPLICAS copies of the sums.
-        constexpr bool bnst = BN_;
-        // (address from scalars at every use: a pointer kept across the tile loop is two more VGPRs the kernel does not have)
-        auto bnl_at = [&](int k) -> float* {
-            const int wvs = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-            const int w_bytes = (p.w_elems * (int)sizeof(T) + 15) & ~15;
-            return reinterpret_cast<float*>(smem + w_bytes + (wvs + 1) * p.wave_lds_bytes - 2 * CP_ * 4) + k;
-        };
-        int bn_rows = (int)p.N;
-        if (bnst) {
-            if (p.bn_nrows) bn_rows = (int)max((int64_t)1, min(*p.bn_nrows, p.N));
-            if (gw == 0 && h == 0) {            // the shift row the sums are about, for the apply kernel (behind the totals rows)
-#pragma unroll
-                for (int sl = 0; sl < NSL; ++sl)
-                    p.bn_sums[(size_t)(2 * MDL_BN_REPLICAS + 2) * CP_ + sl * 32 + i] = p.bn_shift ? p.bn_shift[sl * 32 + i] : 0.0f;
-            }
-        }
-        auto bn_add = [&](int sl, float t0, float t1) {      // this lane's sums over its rows -> the wave's LDS totals (h == 0 lanes)
-            t0 += __shfl_xor(t0, 32);
-            t1 += __shfl_xor(t1, 32);
-            if (h == 0) {
-                *bnl_at(sl * 32 + i) += t0;
-                *bnl_at(CP_ + sl * 32 + i) += t1;
-            }
-        };
-        auto bn_flush = [&]() {
-            if (!bnst) return;
-            wave_lds_fence();
-            float* dst = p.bn_sums + (size_t)(gw % MDL_BN_REPLICAS) * 2 * CP_;
-            if (h == 0) {
-#pragma unroll
-                for (int sl = 0; sl < NSL; ++sl) {
-                    unsafeAtomicAdd(dst + sl * 32 + i, *bnl_at(sl * 32 + i));
-                    unsafeAtomicAdd(dst + CP_ + sl * 32 + i, *bnl_at(CP_ + sl * 32 + i));
-                }
-            }
-        };
         if (R.na >= R.nb) return;
         // The wave walks its groups as one continuous stream: the next group's row pointers are requested
         // at the top of the current group, and the indices / edge-feature words of the next group's first
@@ -162,19 +120,6 @@ __global__ __launch_bounds__(FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? FWD_WA
 #pragma unroll
                         for (int u = 0; u < 4; ++u)
                             if (q + u * WAVE < v1) os[q + u * WAVE] = v[u];
-                    }
-                }
-                if (bnst && G.n0 < bn_rows) {                      // (rare: isolated nodes below the row count; the padding is excluded)
-#pragma unroll
-                    for (int sl = 0; sl < NSL; ++sl) {
-                        const float sh = p.bn_shift ? p.bn_shift[sl * 32 + i] : 0.0f;
-                        float t0 = 0.0f, t1 = 0.0f;
-                        for (int n = G.n0 + h; n < min(ne, bn_rows); n += 2) {
-                            const float v = (float)Elem<T>::ld(x + (int64_t)n * dm.C + sl * 32 + i) - sh;
-                            t0 += v;
-                            t1 = fmaf(v, v, t1);
-                        }
-                        bn_add(sl, t0, t1);
                     }
                 }
                 if (ne >= R.nb) break;
@@ -323,23 +268,13 @@ __global__ __launch_bounds__(FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? FWD_WA
                 for (int r = 0; r < 16; ++r) invr[r] = __shfl(invd, d_row(r, h));
 #pragma unroll
                 for (int sl = 0; sl < NSL; ++sl) {
-                    const float sh = (bnst && p.bn_shift) ? p.bn_shift[sl * 32 + i] : 0.0f;
-                    float t0 = 0.0f, t1 = 0.0f;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int n = G.n0 + d_row(r, h);
                         float a = acc_out[sl][r] * GT::M_SCALE;
                         if (p.aggr == MDL_MEAN) a *= invr[r];
-                        const float v = xr[sl][r] + a;
-                        if (n < G.n1) Elem<T>::st(out + (int64_t)n * dm.C + sl * 32 + i, v);
-                        if (bnst) {
-                            // the statistics of what the BatchNorm will READ: the rounded value, rows that exist only
-                            const float vr = (n < G.n1 && n < bn_rows) ? Elem<T>::rnd(v) - sh : 0.0f;
-                            t0 += vr;
-                            t1 = fmaf(vr, vr, t1);
-                        }
+                        if (n < G.n1) Elem<T>::st(out + (int64_t)n * dm.C + sl * 32 + i, xr[sl][r] + a);
                     }
-                    if (bnst) bn_add(sl, t0, t1);
                 }
             }
             TMARK(11);
@@ -347,7 +282,6 @@ __global__ __launch_bounds__(FWD_THREADS, ((sizeof(T) == 4 && CP_ != 0) ? FWD_WA
             G = GN;
             primed = nextHasEdges;
         }
-        bn_flush();
         TFLUSH(0);
         return;
     }

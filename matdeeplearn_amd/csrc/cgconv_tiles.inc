@@ -69,17 +69,9 @@ struct CgParams {
                         // the saved-gate backward (cgconv_bwd_ab_kernel)
     const int32_t* balance;   // bwd, optional: [N + 1] non-decreasing cost prefix the workgroups' node ranges are balanced on
                               // (mdl_cgconv_balance); null: edges + nodes in front of a node
-    int ldwe;           // bwd: leading dimension of dwe in floats (0: GP) — MdlCgConv.ld_dwe
     int dwe_combine;    // bwd, per-wave kernel: the two waves of a workgroup that share a channel slice combine their dwe sums in LDS
     int rs16;           // bwd, bf16: r_src is a bf16 array accumulated with packed bf16 atomics (mdl_cgconv_bwd_h)
     int flags;          // host side: MDL_DETERMINISTIC / MDL_K3_* bits the caller OR-ed into `dtype`
-    // fwd, optional (mdl_cgconv_fwd_ex): statistics of the layer's OUTPUT for the training-mode BatchNorm1d behind it (cgcnn.py:143)
-    // in the epilogue — per column sum (v - shift) and sum (v - shift)^2 of the ROUNDED outputs over the rows that exist, into
-    // one of the MDL_BN_REPLICAS copies of the sums (layout of mdl_bn_stats; caller zero-fills); the shift row the sums are
-    // about is published behind the sums' totals rows for mdl_bn_apply_n(... | MDL_BN_SHIFT_ROW)
-    float* bn_sums;
-    const float* bn_shift;     // [C] fp32 or null (= 0): any per-column value near the column mean (the previous BatchNorm's beta)
-    const int64_t* bn_nrows;   // device row count of a padded static batch, or null (= N)
     const void* pt;     // W-split kernels: per-node projections P_t = x [W_f,tgt ; W_s,tgt]^T and P_s = x [W_f,src ; W_s,src]^T,
     const void* ps;     // [N, 2Cp] each in the compute dtype (columns f | s), scaled like the packed weights
     int64_t N, E;

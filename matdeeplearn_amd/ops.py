@@ -634,8 +634,6 @@ OPTIONS = {
     "balance": ("_BALANCE", "cost-balanced node ranges for the edge-per-lane CGConv backward (E >= 4e5)"),
     "pad128": ("_PAD128", "C in (96, 128): static 128-channel CGConv kernels on zero-padded rows"),
     "rsrc16": ("_RSRC16", "by-source sums of the CGConv backward in bf16 (packed atomics)"),
-    "cg_bn_stats": ("_CG_BN_STATS", "BatchNorm statistics in the CGConv forward's epilogue (measured time-neutral: off)"),
-    "direct_grads": ("_DIRECT_GRADS", "K3 / K3c add into the final dW layout (measured slower at small batches: off)"),
     "cfconv_fused": ("_CFCONV_FUSED", "K4: the fused CFConv forward"),
     "cfconv_recompute": ("_CFCONV_RECOMPUTE", "K4b: CFConv backward with the filter recomputed (no per-edge activations)"),
     "tn_colsum": ("_TN_COLSUM", "bias gradients out of the TN GEMM"),
@@ -733,7 +731,7 @@ def _take_rsrc(nfloats, device):
 
 class _CGConvFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, edge_attr, w_f, b_f, w_s, b_s, csr, aggr, bn=None, packed=None, split=False, d_norm=None, rbf=None):
+    def forward(ctx, x, edge_attr, w_f, b_f, w_s, b_s, csr, aggr, packed=None, split=False, d_norm=None, rbf=None):
         require_hip(x, edge_attr, w_f, w_s)
         if edge_attr.dtype != x.dtype:
             raise MdlError("cgconv: x (%s) and edge_attr (%s) must share a dtype" % (x.dtype, edge_attr.dtype))
@@ -777,12 +775,8 @@ class _CGConvFn(torch.autograd.Function):
         ctx.wn_t = wn_t
         out = torch.empty_like(x)
         edge_attr = csr.sorted_attr(edge_attr)          # CSR order: the kernels never go through eperm
-        # statistics of the output for the BatchNorm behind the layer, in the kernel's epilogue (bn = (sums buffer, shift)): the
-        # static bf16 kernels only — the caller (cgconv_bn_stats_ok) has checked
-        bn_sums, bn_shift = bn if bn is not None else (None, None)
         args = _lib.cg_args(dtype=dt, flags=sp, aggr=aggr, N=N, E=E, C=Ck, G=G, x=x, edge_attr=edge_attr, rowptr=csr.rowptr, src=csr.src,
-                            tgt=csr.tgt, wpack=wpack, bpack=bpack, out=out, bn_sums=bn_sums, bn_shift=bn_shift,
-                            bn_rows=_true_rows_for(N) if bn_sums is not None else None)
+                            tgt=csr.tgt, wpack=wpack, bpack=bpack, out=out)
         check(_launch_timed("fwd", lambda: L.mdl_cgconv_fwd_ex(args, stream())), "mdl_cgconv_fwd_ex")
         # (d_norm, rbf): the edge features are rbf_expand(d_norm) — the backward then returns dL/dd_norm from the fused distance
         # epilogue of the edge-gradient kernel (mdl_cgconv_bwd_edge) instead of an [E, G] gradient
@@ -802,7 +796,7 @@ class _CGConvFn(torch.autograd.Function):
         launches they always were; a gradient w.r.t. edge_attr (general epilogue, caller's edge order and dtype) or w.r.t. the
         expanded distance (fused epilogue) costs one launch of the edge-gradient kernel on top."""
         need_de = ctx.needs_input_grad[1]
-        need_dd = len(ctx.needs_input_grad) > 11 and ctx.needs_input_grad[11] and ctx.rbf_coeff is not None
+        need_dd = len(ctx.needs_input_grad) > 10 and ctx.needs_input_grad[10] and ctx.rbf_coeff is not None
         de, dd = _cgconv_edge_grads(ctx, g, need_de, need_dd) if (need_de or need_dd) else (None, None)
         grads = _CGConvFn._backward_main(ctx, g)
         return grads[:1] + (de,) + grads[2:] + (dd, None)
@@ -834,29 +828,17 @@ class _CGConvFn(torch.autograd.Function):
             r_src = r_src.view(torch.bfloat16).view(N, 2 * Cp) if rs16 else r_src.view(N, 2 * Cp)
         else:
             r_src = torch.zeros((N, 2 * Cp), dtype=torch.bfloat16 if rs16 else torch.float32, device=x.device)
-        ldw = 2 * C + G
-        direct = node_hip and _DIRECT_GRADS
-        if direct:
-            # K3 and K3c add their partial sums straight into the two Linears' STACKED weight gradient dW [2C, 2C + G] (rows f | s,
-            # columns target | source | edge: MdlCgConv.ld_dwe, MdlCgNode.ld_dwn) and into db [2C]: no assembly kernel, no staging
-            # buffers.  One zero-filled slice of the step's gradient arena; dW_f / dW_s / db_f / db_s are views of it.
-            gbuf = _zeros_grad(2 * C * ldw + 2 * C, x.device)
-            dW = gbuf[:2 * C * ldw].view(2 * C, ldw)
-            db = gbuf[2 * C * ldw:]
-            dwe, dwn, ld_dwe = dW[:, 2 * C:], dW, ldw
-        else:
-            small = _zeros_step((2 * Cp * GP + 2 * Cp + 4 * Cp * C,), x.device)
-            dwe = small[:2 * Cp * GP].view(2 * Cp, GP)
-            db = small[2 * Cp * GP:2 * Cp * GP + 2 * Cp]
-            dwn = small[2 * Cp * GP + 2 * Cp:].view(4 * Cp, C)
-            ld_dwe = 0
+        small = _zeros_step((2 * Cp * GP + 2 * Cp + 4 * Cp * C,), x.device)
+        dwe = small[:2 * Cp * GP].view(2 * Cp, GP)
+        db = small[2 * Cp * GP:2 * Cp * GP + 2 * Cp]
+        dwn = small[2 * Cp * GP + 2 * Cp:].view(4 * Cp, C)
         ws = _workspace(x.device, lib().mdl_cgconv_workspace_bytes(N, E, C, G, dt))
         fl = _dflag()
         # node ranges of equal COST (far sources make a tile dearer): one prefix per batch, shared by all layers
         bal = csr.balance() if (rs16 and _BALANCE and E >= 400000 and not fl) else None
         eargs = _lib.cg_args(dtype=dt, flags=fl | (_k3flag() if rs16 else 0) | sp, aggr=ctx.aggr, N=N, E=E, C=Ck, G=G, x=xk, edge_attr=edge_attr,
                              rowptr=csr.rowptr, src=csr.src, tgt=csr.tgt, wpack=wpack, bpack=bpack, grad_out=gk, r_tgt=r_tgt, r_src=r_src,
-                             r_src_dtype=_lib.MDL_BF16 if rs16 else _lib.MDL_F32, dwe=dwe, ld_dwe=ld_dwe, db=db, workspace=ws,
+                             r_src_dtype=_lib.MDL_BF16 if rs16 else _lib.MDL_F32, dwe=dwe, db=db, workspace=ws,
                              workspace_bytes=ws.numel(), balance=bal)
         check(_launch_timed("bwd", lambda: lib().mdl_cgconv_bwd_ex(eargs, stream())), "mdl_cgconv_bwd_ex")
         # node-level dense part: rows of Wn / dWn = (f_tgt, s_tgt, f_src, s_src)
@@ -864,17 +846,12 @@ class _CGConvFn(torch.autograd.Function):
             wn_t = _node_weights(ctx, C, Cp, torch.float32 if node_x3 else torch.bfloat16, x.device, wf32, ws32)
             dx = torch.empty_like(x)
             nargs = _lib.cg_node_args(dtype=dt, flags=fl | (sp if node_x3 else 0), zero_src=1 if keep is not None else 0, N=N, C=C,
-                                      r_src_dtype=_lib.MDL_BF16 if rs16 else _lib.MDL_F32, ld_dwn=ldw if direct else 0, x=x, grad_out=g,
-                                      r_tgt=r_tgt, r_src=r_src, wn_t=wn_t, dx=dx, dwn=dwn)
+                                      r_src_dtype=_lib.MDL_BF16 if rs16 else _lib.MDL_F32, x=x, grad_out=g, r_tgt=r_tgt, r_src=r_src,
+                                      wn_t=wn_t, dx=dx, dwn=dwn)
             check(_launch_timed("bwd_node", lambda: lib().mdl_cgconv_bwd_node_ex(nargs, stream())), "mdl_cgconv_bwd_node_ex")
             if keep is not None:
                 keep[1] = False                                                                     # handed back zeroed
-            if direct:
-                dW_f, dW_s = dW[:C], dW[C:]
-                db_f = db[:C].to(ctx.wdtypes[0]) if ctx.has_bias[0] else None
-                db_s = db[C:].to(ctx.wdtypes[1]) if ctx.has_bias[1] else None
-            else:
-                dW_f, db_f, dW_s, db_s = _assemble_grads(ctx, dwn, dwe, db, C, G, x.device, timed=True)
+            dW_f, db_f, dW_s, db_s = _assemble_grads(ctx, dwn, dwe, db, C, G, x.device, timed=True)
         elif dt == _lib.MDL_BF16 and Cp == 128 and C % 2 == 0 and N > 0:
             # wide layers (C = 100 / 128): the same products on the streaming kernels.  r_tgt / r_src keep their padded
             # [N, 2 Cp] layout (padded columns are exact zeros), so  dx = g + r_tgt Wn_t + r_src Wn_s  is two library GEMMs on
@@ -905,7 +882,7 @@ class _CGConvFn(torch.autograd.Function):
             dW_s = torch.cat([dWn[C:2 * C], dWn[3 * C:4 * C], dwe[Cp:Cp + C, :G]], dim=1)
             db_f = db[:C].clone() if ctx.has_bias[0] else None
             db_s = db[Cp:Cp + C].clone() if ctx.has_bias[1] else None
-        return dx, None, dW_f.to(ctx.wdtypes[0]), db_f, dW_s.to(ctx.wdtypes[1]), db_s, None, None, None, None, None
+        return dx, None, dW_f.to(ctx.wdtypes[0]), db_f, dW_s.to(ctx.wdtypes[1]), db_s, None, None, None, None
 
 
 def _node_weights(ctx, C, Cp, dtype, device, wf32, ws32):
@@ -961,12 +938,10 @@ def cgconv_prepack(convs, x_dtype, device, want_node=True):
     return [(wbuf[k], bbuf[k], nbuf[k] if want_node else None, (C, G, dt)) for k in range(n)]
 
 
-def cgconv(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr="mean", csr=None, bn_stats=None, packed=None, split=False, dist=None):
+def cgconv(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr="mean", csr=None, packed=None, split=False, dist=None):
     """CGConv forward.  x [N,C], edge_index [2,E], edge_attr [E,G]; returns [N,C].  Differentiable (first order) in
     x, the weights and edge_attr, like upstream's operator; the edge_attr gradient comes back in the caller's edge order and in
     edge_attr's dtype from one extra launch (csrc/cgconv_de.hip), and only when edge_attr requires it.
-    bn_stats = (sums [2 R + 3, C] fp32 zero-filled, shift [C] fp32 or None): the kernel's epilogue also forms the statistics
-    of its output for the BatchNorm behind the layer (callers check cgconv_bn_stats_ok first).
     dist = (d_norm [E] fp32, offsets [G] fp32, coeff): a promise that edge_attr = rbf_expand(d_norm) on these centres (detached:
     edge_attr itself carries no gradient).  The backward then hands d_norm its gradient from the kernel's fused distance epilogue,
     and no [E, G] gradient is ever stored.  Under split=True ("bf16x3") the edge-gradient kernel runs its exact fp32 form."""
@@ -975,10 +950,9 @@ def cgconv(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr="mean", csr=None, 
     if csr is None:
         csr = csr_for(edge_index, x.shape[0])
     if dist is None:
-        return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], bn_stats, packed, split)
+        return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], packed, split)
     d_norm, offsets, coeff = _check_dist("cgconv", dist, edge_attr, "edge_attr")
-    return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], bn_stats, packed, split, d_norm,
-                           (offsets.float(), float(coeff)))
+    return _CGConvFn.apply(x, edge_attr, w_f, b_f, w_s, b_s, csr, _lib.REDUCE[aggr], packed, split, d_norm, (offsets.float(), float(coeff)))
 
 
 def _check_dist(name, dist, edge_attr, what):
@@ -1082,39 +1056,6 @@ def cgconv_dist_grad(x, edge_index, d_norm, w_f, b_f, w_s, b_s, grad_out, aggr="
         _bwd_edge_launch(x.detach().contiguous(), ea, csr, wpack, bpack, grad_out.detach().to(x.dtype).contiguous(), _lib.REDUCE[aggr], C, G,
                          d_sorted=d_sorted, offsets=offsets, coeff=rbf_coeff(start, stop, width), scale=scale, dd=dd)
         return dd if out is not None else _unsort_edges(dd, csr)
-
-
-# BatchNorm statistics in the CGConv forward's epilogue (mdl_cgconv_fwd_ex, bn_sums): OPT-IN.  Measured on the bench batch
-# (profiles/r05_k2_bn_stats_ab.txt, kernel traces of alternating runs): the statistics kernel it removes costs 7.7 us per layer,
-# the forward instantiation that carries the epilogue is 12.5 us per layer slower than the plain one (188.0 vs 175.8 us: it
-# sits at 256 VGPRs with 28 bytes of scratch, the plain kernel at 252 and none) — time-neutral at 8192 graphs and at 100.
-_CG_BN_STATS = False
-# K3 / K3c can add their weight-gradient partial sums straight into the stacked dW [2C, 2C + G] (MdlCgConv.ld_dwe, MdlCgNode.ld_dwn:
-# no mdl_cgconv_assemble_grads launch).  OPT-IN: measured in one box session (profiles/r05_direct_grads_ab.txt) the node kernel's
-# flush into 712-byte rows (every 128-byte atomic instruction straddles two cache lines) costs it +8.5 us at 8192 graphs — what the
-# 7-us assembly kernel cost — and +10 us per layer at the reference's batch size, where that flush IS the kernel: 0.59 vs 0.55 ms/step.
-_DIRECT_GRADS = False
-
-
-def cgconv_bn_stats_ok(x, edge_attr, csr):
-    """The CGConv forward can form the statistics of its output for the BatchNorm1d behind it: the static bf16 kernels
-    (C in {32, 64}, G = 50, edge features in CSR order, 16-byte aligned rows), training with batch statistics, not in
-    deterministic mode (there the one-workgroup statistics kernel gives the run-to-run reproducible sums)."""
-    return (_CG_BN_STATS and not _DET and x.is_cuda and x.dtype == torch.bfloat16 and edge_attr.dtype == torch.bfloat16 and x.dim() == 2
-            and x.shape[1] in (32, 64) and edge_attr.shape[1] == 50 and csr.eperm is None and csr.E > 0 and x.shape[0] >= 2
-            and x.is_contiguous() and x.data_ptr() % 16 == 0 and edge_attr.data_ptr() % 4 == 0)
-
-
-def cgconv_bn(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr, csr, bn_weight, bn_bias, running_mean, running_var, eps, momentum,
-              shift=None, packed=None):
-    """BatchNorm1d(train)(cgconv(...)) — cgcnn.py:136-145 — with the statistics pass over [N, C] folded into the conv kernel's
-    epilogue: the sums are formed about `shift` ([C] fp32 near the column means: the beta of the BatchNorm in FRONT of the layer,
-    None = 0) and normalised by mdl_bn_apply_n(MDL_BN_SHIFT_ROW)."""
-    C = x.shape[1]
-    R = lib().mdl_bn_sums_rows()
-    buf = _zeros_step((R + 3, C), x.device)                  # sums (copies + totals) | shift row | save (mean, invstd)
-    y = cgconv(x, edge_index, edge_attr, w_f, b_f, w_s, b_s, aggr, csr=csr, bn_stats=(buf, _f32c(shift)), packed=packed)
-    return _BatchNormTrain.apply(y, bn_weight, bn_bias, running_mean, running_var, eps, momentum, buf)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2452,12 +2393,11 @@ def bn_sums_rows():
 
 class _BatchNormTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, pre=None):
+    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum):
         N, C = x.shape
         dt = dtype_code(x)
         R = lib().mdl_bn_sums_rows()
-        # pre: [R + 3, C] buffer whose sums the PRODUCER of x has already formed about the shift in row R (cgconv_bn)
-        buf = _zeros_step((R + 2, C), x.device) if pre is None else pre       # rows 0..R-1: sums (copies + totals) [| shift] | save
+        buf = _zeros_step((R + 2, C), x.device)                               # rows 0..R-1: sums (copies + totals) | save
         sums, save = buf[:R], buf[-2:]
         gw, gb = _f32c(weight), _f32c(bias)
         y = torch.empty_like(x)
@@ -2465,11 +2405,9 @@ class _BatchNormTrain(torch.autograd.Function):
         # (statistics + apply as ONE launch for few rows was built and measured slower at the reference's batch size — 0.54 vs
         # 0.49 ms/step: C / 8 workgroups walking all rows twice are a longer dependent chain than two wide launches;
         # experiments/patches/bn_one_launch.patch)
-        if pre is None:
-            check(lib().mdl_bn_stats_n(ptr(x), ptr(sums), N, C, ptr(nd), dt | _dflag(), stream()), "mdl_bn_stats")
+        check(lib().mdl_bn_stats_n(ptr(x), ptr(sums), N, C, ptr(nd), dt | _dflag(), stream()), "mdl_bn_stats")
         check(lib().mdl_bn_apply_n(ptr(x), ptr(sums), ptr(gw), ptr(gb), ptr(save), ptr(running_mean), ptr(running_var),
-                                   ptr(y), N, C, float(eps), float(momentum), ptr(nd),
-                                   dt | (_lib.MDL_BN_SHIFT_ROW if pre is not None else 0), stream()), "mdl_bn_apply")
+                                   ptr(y), N, C, float(eps), float(momentum), ptr(nd), dt, stream()), "mdl_bn_apply")
         ctx.n_dev = nd
         ctx.save_for_backward(x, save, gw)
         ctx.has = (weight is not None, bias is not None)
@@ -2491,7 +2429,7 @@ class _BatchNormTrain(torch.autograd.Function):
               "mdl_bn_bwd_apply")
         dgamma = sums[R - 1].to(ctx.wdt) if ctx.has[0] else None          # totals row pair published by bwd_apply
         dbeta = sums[R - 2].to(ctx.wdt) if ctx.has[1] else None
-        return dx, dgamma, dbeta, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, None, None
 
 
 class _LinearReluBN(torch.autograd.Function):

@@ -29,7 +29,6 @@ LN2 = float(torch.tensor(0.6931471805599453, dtype=torch.float32))       # Gate<
 #   static64               edge_lane      out 1.00  dx 1.49  dW_f 1.56  db_f 0.83  dW_s 1.20  db_s 0.82
 #   static64               deterministic  out 1.00  dx 1.37  dW_f 1.32  db_f 1.00  dW_s 1.29  db_s 1.00
 #   static64               rsrc16_off     out 1.00  dx 1.22  dW_f 1.01  db_f 1.00  dW_s 1.04  db_s 1.00
-#   static64               direct_grads   out 1.00  dx 1.31  dW_f 1.44  db_f 1.00  dW_s 1.29  db_s 1.00
 #   far_sources            per_wave       out 1.00  dx 1.87  dW_f 1.25  db_f 1.00  dW_s 1.32  db_s 1.00
 #   far_sources            edge_lane      out 1.00  dx 1.70  dW_f 1.48  db_f 0.74  dW_s 1.31  db_s 0.62
 #   partial_group                         out 1.00  dx 1.30  dW_f 1.59  db_f 1.00  dW_s 1.48  db_s 1.00

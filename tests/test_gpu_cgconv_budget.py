@@ -66,11 +66,10 @@ def _check(name, label="", variant=None, k3=None, det=False, **options):
     ("edge_lane", dict(variant="edge_lane", k3=2)),
     ("deterministic", dict(det=True, k3=3)),
     ("rsrc16_off", dict(variant="per_wave", k3=1, rsrc16=False)),
-    ("direct_grads", dict(variant="per_wave", k3=1, direct_grads=True)),
 ])
 def test_static_64(label, kw):
     """C 64, G 50, n 200: the static kernels; every backward edge pass (per-wave, edge-per-lane, deterministic shape), fp32
-    by-source sums, weight gradients added straight into the final layout."""
+    by-source sums."""
     _check("static64", label, **kw)
 
 
