@@ -683,11 +683,45 @@ int mdl_set2set_bwd(const void* x, const int32_t* rowptr, const float* w_ih, con
  *      else:   v <- 0, alpha <- alpha_start, dt <- dt f_dec, n_pos <- 0
  *   3. v <- v + dt f;  dr = dt v, scaled by maxstep / |dr| where |dr| (norm over the structure) > maxstep;  pos += dr;  steps += 1.
  * Sums by wave shuffles, then the waves through LDS in wave order: no atomics, bitwise repeatable.  Caller owns every buffer; no
- * allocation, no synchronisation.  B == 0 or N == 0 returns 0 without a launch. */
+ * allocation, no synchronisation.  B == 0 or N == 0 returns 0 without a launch.
+ *
+ * Plain mode, image_ptr == NULL: the above, ONE launch; every argument from image_ptr to climber is ignored.
+ *
+ * Band mode, image_ptr != NULL: a nudged-elastic-band step (improved tangent, Henkelman & Jonsson, J. Chem. Phys. 113, 9978;
+ * climbing image, 113, 9901) — FIRE on bands whose force is projected first.  TWO stream-ordered launches: the band force of
+ * every image (csrc/neb.hip, one workgroup per image), then the kernel of plain mode over the B BANDS, reading band_force in the
+ * place of force.  A batch of I images (structures) in B bands: band b owns the consecutive images band_ptr[b] ..
+ * band_ptr[b + 1] - 1 (band_ptr [B + 1] int64, non-decreasing, clamped to [0, I]), all with the same atom count n_b; image s
+ * owns the atoms image_ptr[s] .. image_ptr[s + 1] - 1 (image_ptr [I + 1] int64, non-decreasing, clamped to [0, N]), so
+ * atom j of image s + 1 is row image_ptr[s + 1] + j.  The caller passes node_ptr[b] = image_ptr[band_ptr[b]]: a band moves with
+ * one dt, one alpha, one P = F.v and one latch (converged: the largest per-atom |F_band| over all its images < fmax[b]); maxstep
+ * bounds the norm of the whole band's displacement.  The first and the last image of a band are its fixed end points: the
+ * caller marks their atoms in `fixed`, and their band_force rows are zero whatever `fixed` says.
+ *   force [N, 3] fp32: the true force;  energy [I] fp32;  cell [I, 3, 3] fp64 (rows are lattice vectors);  pbc [I] int32 (bit a:
+ *   axis a periodic);  spring [B] fp64;  climb [B] uint8: read.
+ *   band_force [N, 3] fp32, tangent_force, seg_len [I] fp64, climber [B] int32: written.
+ * Interior image i of band b (E promoted to fp64, F with the rows of fixed atoms zeroed, all arithmetic fp64):
+ *   t+ = R(i + 1) - R(i), t- = R(i) - R(i - 1) per atom, each wrapped to its minimum image in cell[i]: f = d C^-1 (adjugate over
+ *        determinant), f_k -= rint(f_k) on the periodic axes, d = f C; no wrap where det C == 0.  Exact only while an atom moves
+ *        less than half a cell height between neighbouring images: the caller's condition.
+ *   t = a t+ + b t-:  E(i+1) > E(i) > E(i-1): (1, 0);  E(i+1) < E(i) < E(i-1): (0, 1);  else, hi / lo the larger / smaller of
+ *        |E(i+1) - E(i)| and |E(i-1) - E(i)|: (hi, lo) if E(i+1) > E(i-1), else (lo, hi).
+ *   |t|^2 = a^2 |t+|^2 + 2 a b t+.t- + b^2 |t-|^2,  F.t^ = (a F.t+ + b F.t-) / |t|   (five sums, one reduction)
+ *   F_band = F - (F.t^) t^ + spring[b] (|t+| - |t-|) t^;  the climber: F_band = F - 2 (F.t^) t^.  |t|^2 == 0: F_band = F.
+ *   The climber of band b: its interior image of largest energy, lowest index on ties, where climb[b] != 0; climber[b] is its
+ *   index in the batch, -1 where there is none.  End images and fixed atoms get zero rows; a band of fewer than three images is
+ *   all zero rows, so the second launch latches it (no force on a free atom).
+ *   tangent_force[i] = F.t^ (0 for end images); seg_len[i] = |t-| (0 for a band's first image; for its last, the distance to the
+ *   one before it).  band_force is computed in fp64 and rounded once.  Rows of no band are not written.  A neighbour counts only
+ *   if it has the image's atom count (else the image is treated as an end image): no row outside [0, N) is read whatever the
+ *   pointers hold.  I >= 0, every band-mode pointer non-NULL, band_force != force, max(I, B) < 2^31: MDL_E_ARG / MDL_E_UNSUPP.
+ * No atomics, every decision taken by every lane from the same numbers: bitwise repeatable, a band alone or in any batch. */
 int mdl_fire_step(double* pos, double* vel, const float* force, const uint8_t* fixed, const int64_t* node_ptr, int64_t N,
                   int64_t B, const double* fmax, double* dt, double* alpha, int32_t* n_pos, int32_t* steps, int32_t* done,
                   float* fmax_seen, int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double dt_max,
-                  double maxstep, mdlStream_t stream);
+                  double maxstep, const int64_t* image_ptr, const int64_t* band_ptr, int64_t I, const float* energy,
+                  const double* cell, const int32_t* pbc, const double* spring, const uint8_t* climb, float* band_force,
+                  double* tangent_force, double* seg_len, int32_t* climber, mdlStream_t stream);
 
 /* mdl_fire_cell_step: the same update over the atoms AND the cell of every structure, N + 3 rows per structure, ONE launch.
  * Cells are row-vector matrices.  C0 = cell0[b] is the cell the relaxation started from; the deformation gradient F = deform[b]

@@ -14,6 +14,8 @@
 //                   every run.  Lane 0 alone reads and writes the per-structure state, so no lane can see a half-updated one.
 //                   A converged structure (latched before, or max_i |f_i| < fmax, or no force on a free atom) gets done = 1 and
 //                   fmax_seen; nothing else of it is written.
+//                   Band mode (image_ptr != NULL): the band-force launch of csrc/neb.hip goes first, and the same
+//                   fire_kernel<false> then moves BANDS on the force that launch wrote — a nudged-elastic-band step.
 //   mdl_fire_cell_step   fire_kernel<true>: the same update over the atoms and the cell: the rows s_i (pos_i = F s_i) and the three
 //                   rows of W = cf F, F the deformation gradient of the cell the relaxation started from.  Same workgroup, same
 //                   sums; the 3x3 algebra (F^-1 through the adjugate, S F^-T, det cell) is done by every lane from the same nine
@@ -53,21 +55,6 @@ struct FireArgs {
     const double *cell_factor, *smax;
     float* smax_seen;
 };
-
-// row-major 3x3: the adjugate (inverse times determinant) and the determinant
-__device__ __forceinline__ double adjugate3(const double* m, double* adj) {
-#pragma clang fp contract(off)
-    adj[0] = m[4] * m[8] - m[5] * m[7];
-    adj[1] = m[2] * m[7] - m[1] * m[8];
-    adj[2] = m[1] * m[5] - m[2] * m[4];
-    adj[3] = m[5] * m[6] - m[3] * m[8];
-    adj[4] = m[0] * m[8] - m[2] * m[6];
-    adj[5] = m[2] * m[3] - m[0] * m[5];
-    adj[6] = m[3] * m[7] - m[4] * m[6];
-    adj[7] = m[1] * m[6] - m[0] * m[7];
-    adj[8] = m[0] * m[4] - m[1] * m[3];
-    return m[0] * adj[0] + m[1] * adj[3] + m[2] * adj[6];
-}
 
 // CELL = false: the atoms alone (include/mdl_hip.h, mdl_fire_step); free_cell is false at compile time, and no cell matrix, no
 // `scaled` row and no cell pointer is touched.
@@ -375,13 +362,22 @@ extern "C" int mdl_fire_cell_step(double* pos, double* cell, double* scaled, dou
 extern "C" int mdl_fire_step(double* pos, double* vel, const float* force, const uint8_t* fixed, const int64_t* node_ptr, int64_t N,
                              int64_t B, const double* fmax, double* dt, double* alpha, int32_t* n_pos, int32_t* steps, int32_t* done,
                              float* fmax_seen, int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha,
-                             double dt_max, double maxstep, mdlStream_t stream) {
+                             double dt_max, double maxstep, const int64_t* image_ptr, const int64_t* band_ptr, int64_t I,
+                             const float* energy, const double* cell, const int32_t* pbc, const double* spring, const uint8_t* climb,
+                             float* band_force, double* tangent_force, double* seg_len, int32_t* climber, mdlStream_t stream) {
     using namespace mdl;
     const FireConst c = {n_min, f_inc, f_dec, alpha_start, f_alpha, dt_max, maxstep};
     if (const int err = fire_check("mdl_fire_step", N, B, c)) return err;
     if (B == 0 || N == 0) return MDL_OK;
     MDL_REQUIRE(pos && vel && force && node_ptr && fmax && dt && alpha && n_pos && steps && done && fmax_seen, MDL_E_ARG,
                 "mdl_fire_step: null pointer");
+    if (image_ptr) {
+        // band mode: the band force of every image first (csrc/neb.hip), then the same launch as below over the B bands on it
+        const NebArgs nb = {pos,  force, fixed,  image_ptr, band_ptr,   N,             I,       B,      energy,
+                            cell, pbc,   spring, climb,     band_force, tangent_force, seg_len, climber};
+        if (const int err = neb_band_force("mdl_fire_step", nb, (hipStream_t)stream)) return err;
+        force = band_force;
+    }
     const FireArgs a = {pos, vel, force, fixed, node_ptr, N, fmax, dt, alpha, n_pos, steps, done, fmax_seen};   // the cell's fields: null
     hipLaunchKernelGGL(fire_kernel<false>, dim3((unsigned)B), dim3(FIRE_THREADS), 0, (hipStream_t)stream, a, c, 0.0);
     return check_launch("mdl_fire_step");

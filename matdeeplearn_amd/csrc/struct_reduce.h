@@ -1,6 +1,7 @@
-// struct_reduce.h — the workgroup-per-structure reduction of the integrators (csrc/relax.hip, csrc/md.hip): one workgroup of 256
-// lanes owns one structure; its sums are formed by a wave64 shuffle tree, then the four waves through LDS in wave order — no
-// atomics, the same bits on every run and in every batch.
+// struct_reduce.h — the workgroup-per-structure reduction of the integrators (csrc/relax.hip, csrc/md.hip, csrc/neb.hip): one
+// workgroup of 256 lanes owns one structure; its sums are formed by a wave64 shuffle tree, then the four waves through LDS in wave
+// order — no atomics, the same bits on every run and in every batch.  Also what relax.hip and neb.hip share: the 3x3 adjugate and
+// the operands of the band-force launch that mdl_fire_step makes in band mode.
 #pragma once
 #include "mdl_common.h"
 
@@ -33,5 +34,38 @@ __device__ __forceinline__ void block_reduce(double* v, double (*red)[K]) {
         v[k] = t;
     }
 }
+
+// row-major 3x3: the adjugate (inverse times determinant) and the determinant
+__device__ __forceinline__ double adjugate3(const double* m, double* adj) {
+#pragma clang fp contract(off)
+    adj[0] = m[4] * m[8] - m[5] * m[7];
+    adj[1] = m[2] * m[7] - m[1] * m[8];
+    adj[2] = m[1] * m[5] - m[2] * m[4];
+    adj[3] = m[5] * m[6] - m[3] * m[8];
+    adj[4] = m[0] * m[8] - m[2] * m[6];
+    adj[5] = m[2] * m[3] - m[0] * m[5];
+    adj[6] = m[3] * m[7] - m[4] * m[6];
+    adj[7] = m[1] * m[6] - m[0] * m[7];
+    adj[8] = m[0] * m[4] - m[1] * m[3];
+    return m[0] * adj[0] + m[1] * adj[3] + m[2] * adj[6];
+}
+
+// the band mode of mdl_fire_step (include/mdl_hip.h): csrc/neb.hip checks these operands and launches the band-force kernel
+struct NebArgs {
+    const double* pos;
+    const float* force;
+    const uint8_t* fixed;
+    const int64_t *image_ptr, *band_ptr;
+    int64_t N, I, B;
+    const float* energy;
+    const double* cell;
+    const int32_t* pbc;
+    const double* spring;
+    const uint8_t* climb;
+    float* band_force;
+    double *tangent_force, *seg_len;
+    int32_t* climber;
+};
+int neb_band_force(const char* fn, const NebArgs& a, hipStream_t stream);
 
 }  // namespace mdl

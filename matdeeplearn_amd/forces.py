@@ -28,7 +28,9 @@ launch (ops.fire_step, csrc/relax.hip), every structure with its own time step a
 the cell with the atoms: the same update over the atoms' rows and the three rows of the deformation gradient, driven by the strain
 gradient of energy_forces_stress (ops.fire_cell_step), still one launch per step.  md follows the forces at a temperature: BAOAB,
 NVE or Langevin, one launch per step too (ops.md_step, csrc/md.hip), with counter-based noise, so a structure's trajectory is the
-same alone and in any batch."""
+same alone and in any batch.  neb finds the barrier between two minima: the images of nudged elastic bands are the structures of ONE
+ForceField, the band force (improved tangent, springs, climbing image) of every image is one launch (csrc/neb.hip) and FIRE then
+moves every band as one object (ops.neb_step: the band mode of mdl_fire_step); interpolate_band makes a band from two end points."""
 import collections
 import math
 
@@ -380,13 +382,14 @@ def _per_structure(v, B, dev, who, what):
     return torch.full((B,), float(v), dtype=torch.float64, device=dev)
 
 
-def _relax(who, model, structs, dist_range, bounds, steps, rebuild_every, check_every, fixed, dt, const, ff_args, cell=None):
-    """relax and relax_cell (`who`) behind their arguments: the checks, the ForceField, the rebuild / evaluate / step loop and the
-    evaluation at the returned geometry.  bounds: ((name, value), ...) of the convergence criteria; const: the constants of the
+def _relax(who, model, structs, dist_range, bounds, steps, rebuild_every, check_every, fixed, dt, const, ff_args, cell=None, band=None):
+    """relax, relax_cell and neb (`who`) behind their arguments: the checks, the ForceField, the rebuild / evaluate / step loop and
+    the evaluation at the returned geometry.  bounds: ((name, value), ...) of the convergence criteria; const: the constants of the
     step; cell: None (ops.fire_step on the forces alone), or relax_cell's (cell_free, cell_factor) (ops.fire_cell_step on forces
-    and strain gradient).  Returns (the ForceField, the state, a probe — a copy of the state with every latch set, stepped once
-    at the returned geometry: with every latch set the integrator writes its criteria from its own pass 1 and nothing else —, the
-    bounds as [B] float64 tensors, what that last evaluation returned)."""
+    and strain gradient); band: None, or neb's (band_ptr as a host array, spring, climb, climb_after) (ops.neb_step: the state
+    and the bounds are then per BAND, the structures are the images).  Returns (the ForceField, the state, a probe — a copy of the
+    state with every latch set, stepped once at the returned geometry: with every latch set the integrator writes its criteria
+    from its own pass 1 and nothing else —, the bounds as [B] float64 tensors, what that last evaluation returned)."""
     _accepted(model, dist_range)
     if model.training:
         raise ops.MdlError("%s: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
@@ -398,13 +401,19 @@ def _relax(who, model, structs, dist_range, bounds, steps, rebuild_every, check_
         raise ops.MdlError("%s: max_deform must be in (0, 1) (got %r)" % (who, const["max_deform"]))
     ff = ForceField(model, structs, dist_range, *ff_args)
     dev, N, B = ff.positions.device, ff.positions.shape[0], ff.node_ptr.numel() - 1
-    bounds = [_per_structure(v, B, dev, who, name) for name, v in bounds]
+    n_state = B if band is None else len(band[0]) - 1           # what has a state and a bound: the structures, or neb's bands
+    bounds = [_per_structure(v, n_state, dev, who, name) for name, v in bounds]
     if fixed is not None:
         fixed = (fixed.detach() if torch.is_tensor(fixed) else torch.from_numpy(np.asarray(fixed))).to(dev)
         if tuple(fixed.shape) != (N,):
             raise ops.MdlError("%s: fixed must be an [N] mask with N = %d (got %s)" % (who, N, tuple(fixed.shape)))
         fixed = (fixed != 0).to(torch.uint8)
-    if cell is None:
+    if band is not None:
+        band_ptr, spring, climb, climb_after = band
+        state = ops.neb_state(ff.node_ptr, torch.from_numpy(np.asarray(band_ptr, dtype=np.int64)).to(dev), fixed, dt, const["alpha_start"])
+        spring = _per_structure(spring, n_state, dev, who, "spring")
+        climb = _per_structure(climb, n_state, dev, who, "climb") != 0
+    elif cell is None:
         state = ops.fire_state(B, dt, const["alpha_start"], dev)
     else:
         cell_free, cell_factor = cell
@@ -427,7 +436,11 @@ def _relax(who, model, structs, dist_range, bounds, steps, rebuild_every, check_
         if n_eval > 0 and rebuild_every > 0 and n_eval % rebuild_every == 0:
             ff.rebuild()
         n_eval += 1
-        if cell is None:
+        if band is not None:
+            out = ff.evaluate()
+            ops.neb_step(ff.positions, vel, out[1], _scalar_energy(out[0], ff.output_index), ff.cell, ff.pbc, st, *bounds, spring,
+                         climb & (st.steps >= climb_after), **const)
+        elif cell is None:
             out = ff.evaluate()
             ops.fire_step(ff.positions, vel, out[1], ff.node_ptr, st, *bounds, fixed, **const)
         else:
@@ -484,6 +497,108 @@ def relax_cell(model, structs, dist_range, fmax=0.05, smax=1e-3, steps=200, rebu
     stress = _per_volume(strain, ff.cell, ff.pbc)
     smax_seen = torch.where(torch.isnan(stress).flatten(1).any(1), torch.full_like(probe.smax_seen, float("nan")), probe.smax_seen)
     return CellRelaxResult(ff.positions, ff.cell, energy, f, stress, converged, state.steps, probe.fmax_seen, smax_seen, state.done, ff.node_ptr)
+
+
+NEBResult = collections.namedtuple("NEBResult", "positions energy forces band_forces converged steps fmax climber barrier tangent_force "
+                                                "path node_ptr band_ptr")
+
+
+def _scalar_energy(pred, output_index):
+    """the energy whose negative gradient the forces are, [B] fp32: the prediction, the chosen output or the sum over the outputs"""
+    if pred.dim() == 1:
+        return pred
+    return pred[:, int(output_index)] if output_index is not None else pred.sum(1)
+
+
+def _min_image(d, cell, pbc):
+    """displacements d [n, 3] wrapped to their minimum image: fractional coordinates rounded on the periodic axes (host, fp64)"""
+    cell, per = np.asarray(cell, dtype=np.float64), np.broadcast_to(np.asarray(pbc, dtype=bool).reshape(-1), 3)
+    if not per.any() or np.linalg.det(cell) == 0.0:
+        return d
+    f = d @ np.linalg.inv(cell)
+    f[:, per] -= np.rint(f[:, per])
+    return f @ cell
+
+
+def interpolate_band(initial, final, n_images):
+    """The n_images structures of a band from `initial` to `final` (dict(positions, numbers, cell, pbc) each), end points included:
+    positions linear in the minimum-image displacement final - initial, numbers, cell and pbc those of `initial` (the last image
+    is `final` up to lattice vectors).  Host numpy.  MdlError where the two differ in atom count, numbers, cell or pbc."""
+    n_images = int(n_images)
+    if n_images < 2:
+        raise ops.MdlError("interpolate_band: n_images must be >= 2 (got %d)" % n_images)
+    p0, p1 = np.asarray(initial["positions"], dtype=np.float64), np.asarray(final["positions"], dtype=np.float64)
+    if p0.shape != p1.shape or p0.ndim != 2 or p0.shape[1] != 3:
+        raise ops.MdlError("interpolate_band: initial and final must have the same atoms, [n, 3] positions (got %s and %s)" % (p0.shape, p1.shape))
+    if not np.array_equal(np.asarray(initial["numbers"]), np.asarray(final["numbers"])):
+        raise ops.MdlError("interpolate_band: initial and final differ in their atomic numbers")
+    no_cell, no_pbc = np.zeros((3, 3)), np.zeros(3, dtype=bool)
+    cells = [np.asarray(no_cell if s.get("cell") is None else s["cell"], dtype=np.float64).reshape(3, 3) for s in (initial, final)]
+    pbcs = [np.broadcast_to(np.asarray(no_pbc if s.get("pbc") is None else s["pbc"], dtype=bool).reshape(-1), 3) for s in (initial, final)]
+    if not np.array_equal(cells[0], cells[1]) or not np.array_equal(pbcs[0], pbcs[1]):
+        raise ops.MdlError("interpolate_band: initial and final differ in cell or pbc")
+    d = _min_image(p1 - p0, cells[0], pbcs[0])
+    return [dict(initial, positions=p0 + (k / (n_images - 1)) * d) for k in range(n_images)]
+
+
+def neb(model, bands, dist_range, fmax=0.05, steps=200, spring=1.0, climb=True, climb_after=0, rebuild_every=1, fixed=None, dt=0.1,
+        dt_max=1.0, maxstep=0.2, n_min=5, f_inc=1.1, f_dec=0.5, alpha=0.1, f_alpha=0.99, check_every=10, radius=8.0, max_neighbors=12,
+        dictionary=None, output_index=None):
+    """Minimum-energy paths and saddle points in the model's prediction: nudged elastic bands (improved tangent, Henkelman &
+    Jonsson, J. Chem. Phys. 113, 9978; climbing image, 113, 9901) over the forces of ONE ForceField that holds every image of
+    every band, moved by FIRE with a band as one object — one evaluation and one call (ops.neb_step: the band force of every image
+    in one launch, the update of every band in a second) per step.
+
+    model, dist_range, rebuild_every, check_every, radius, max_neighbors, dictionary, output_index and FIRE's constants   as relax;
+                  the model must be in eval().  With several outputs the energy of the band force is the chosen output, or the sum
+    bands         a list of bands, each a list of structures (interpolate_band makes one from two end points): the images, all
+                  with the same atoms in the same order; the first and the last image of a band stay where they are.  A band of
+                  fewer than three images has nothing to move and comes back converged
+    fmax          a band is converged once the largest per-atom band force over all its images is below this (a number, or one
+                  per band); it is then frozen as relax freezes a structure
+    steps         at most this many updates (a band moves with one time step: steps counts per band)
+    spring        the spring constant along the tangent, a number or one per band (energy per length squared)
+    climb         a number / bool or one per band: the interior image of largest energy (lowest index on ties) feels the true force
+                  with its tangent component inverted and no spring, so it converges to the saddle point
+    climb_after   climbing starts once a band has made this many updates
+    fixed         [N] mask over the atoms of all images in order, or None; the atoms of the end images are fixed anyway
+    maxstep       bounds the norm of a whole band's displacement per step
+
+    Displacements between neighbouring images are wrapped to their minimum image: an atom must move less than half a cell height
+    between neighbours.  Every image has its own neighbour lists (rebuilt together when due), so the energy along a band is only
+    piecewise smooth: two images whose lists differ sit on different smooth functions, the fixed-topology caveat of
+    energy_and_forces; rebuild_every=0 holds the lists of the initial band.  After the last update everything is evaluated once
+    more, so the results belong to the returned positions.
+    Returns NEBResult(positions [N, 3] float64, energy [I] fp32, forces [N, 3] fp32 (true), band_forces [N, 3] fp32, converged [B]
+    bool, steps [B] int32, fmax [B] fp32 (largest per-atom band force), climber [B] int32 (image index in the batch, -1: none),
+    barrier [B] fp32 (largest interior energy minus the first image's; NaN without an interior image), tangent_force [I] float64
+    (F.t^), path [I] float64 (cumulative distance along the band), node_ptr [I + 1], band_ptr [B + 1] int64), device tensors.
+    With ops.deterministic() two calls return the same bits."""
+    who = "neb"
+    bands = [list(b) for b in bands]
+    if not bands:
+        raise ops.MdlError("%s: bands must be a non-empty list of lists of structures" % who)
+    band_ptr = np.concatenate([[0], np.cumsum([len(b) for b in bands])]).astype(np.int64)
+    for b, band in enumerate(bands):
+        counts = [len(np.asarray(s["positions"])) for s in band]
+        if len(set(counts)) > 1:
+            raise ops.MdlError("%s: the images of band %d have unequal atom counts %s" % (who, b, counts))
+    if int(climb_after) < 0:
+        raise ops.MdlError("%s: climb_after must be >= 0" % who)
+    const = dict(n_min=n_min, f_inc=f_inc, f_dec=f_dec, alpha_start=alpha, f_alpha=f_alpha, dt_max=dt_max, maxstep=maxstep)
+    ff, state, probe, (fmax_t,), (pred, f) = _relax(who, model, [s for band in bands for s in band], dist_range, (("fmax", fmax),), steps,
+                                                    rebuild_every, check_every, fixed, dt, const,
+                                                    (radius, max_neighbors, dictionary, output_index), None,
+                                                    (band_ptr, spring, climb, int(climb_after)))
+    energy = _scalar_energy(pred, output_index)
+    fm = probe.fmax_seen.double()
+    converged = (state.done != 0) | (fm < fmax_t) | ~(fm > 0)
+    nan = torch.full((1,), float("nan"), dtype=energy.dtype, device=energy.device)
+    spans = list(zip(band_ptr[:-1].tolist(), band_ptr[1:].tolist()))
+    barrier = torch.cat([(energy[i0 + 1:i1 - 1].max() - energy[i0]).view(1) if i1 - i0 >= 3 else nan for i0, i1 in spans])
+    path = torch.cat([probe.seg_len[i0:i1].cumsum(0) for i0, i1 in spans])
+    return NEBResult(ff.positions, energy, f, probe.band_force, converged, state.steps, probe.fmax_seen, probe.climber, barrier,
+                     probe.tangent_force, path, ff.node_ptr, state.band_ptr)
 
 
 # eV, Angstrom and atomic mass units: the time unit is A sqrt(amu / eV) = 10.18 fs.  dt = 2 * EV_A_AMU.fs is two femtoseconds,

@@ -2739,6 +2739,34 @@ _FIRE_KINDS = {"fire_step": (FIRE_CONSTANTS, FireState, "fire_state", _FIRE_CELL
                "fire_cell_step": (FIRE_CELL_CONSTANTS, FireCellState, "fire_cell_state", _FIRE_CELL_FIELDS)}
 
 
+class NebState:
+    """State of neb_step for I images in B bands: the FireState fields, [B], one set per BAND (dt, alpha, n_pos, steps, done,
+    fmax_seen: the largest per-atom |F_band| of the band); the layout — image_ptr [I + 1], band_ptr [B + 1], band_node_ptr [B + 1]
+    (= image_ptr[band_ptr]: the atoms of a band) int64 and fixed [N] uint8 (the caller's mask OR every atom of an end image) —;
+    and what every call writes: climber [B] int32 (the climbing image's index in the batch, -1: none), tangent_force [I] float64
+    (F.t^, 0 for end images), seg_len [I] float64 (the distance to the image before; 0 for a band's first) and band_force [N, 3]
+    float32 (the projected force the update used)."""
+
+    __slots__ = FireState.__slots__ + ("image_ptr", "band_ptr", "band_node_ptr", "fixed", "climber", "tangent_force", "seg_len", "band_force")
+
+    def __init__(self, *fields):
+        if len(fields) != len(self.__slots__):
+            raise MdlError("NebState: %d fields (%s)" % (len(self.__slots__), ", ".join(self.__slots__)))
+        for k, v in zip(self.__slots__, fields):
+            setattr(self, k, v)
+
+    def clone(self):
+        return NebState(*[getattr(self, k).clone() for k in self.__slots__])
+
+
+_FIRE_KINDS["neb_step"] = (FIRE_CONSTANTS, NebState, "neb_state", _FIRE_CELL_FIELDS[:len(FireState.__slots__)])
+# the fields NebState adds: (field, dtype, shape from (N, I, B))
+_NEB_FIELDS = (("image_ptr", torch.int64, lambda N, I, B: (I + 1,)), ("band_ptr", torch.int64, lambda N, I, B: (B + 1,)),
+               ("fixed", torch.uint8, lambda N, I, B: (N,)), ("climber", torch.int32, lambda N, I, B: (B,)),
+               ("tangent_force", torch.float64, lambda N, I, B: (I,)), ("seg_len", torch.float64, lambda N, I, B: (I,)),
+               ("band_force", torch.float32, lambda N, I, B: (N, 3)))
+
+
 def _fire_args(who, pos, vel, force, node_ptr, state, bounds, fixed, constants, cell=None, strain_grad=None):
     """The argument checks of fire_step and fire_cell_step (`who`: the name every message starts with; cell and strain_grad belong
     to fire_cell_step alone; bounds: (name, a number or a [B] float64 tensor) each).  Returns (the constants with their defaults,
@@ -2802,7 +2830,7 @@ def fire_step(pos, vel, force, node_ptr, state, fmax, fixed=None, **constants):
     check(lib().mdl_fire_step(ptr(pos), ptr(vel), ptr(force.contiguous()), ptr(fixed), ptr(node_ptr.contiguous()), N, B, ptr(fmax),
                               ptr(state.dt), ptr(state.alpha), ptr(state.n_pos), ptr(state.steps), ptr(state.done), ptr(state.fmax_seen),
                               int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
-                              float(c["dt_max"]), float(c["maxstep"]), stream()), "mdl_fire_step")
+                              float(c["dt_max"]), float(c["maxstep"]), None, None, 0, *([None] * 9), stream()), "mdl_fire_step")   # no band
     return state
 
 
@@ -2857,6 +2885,99 @@ def fire_cell_step(pos, cell, vel, force, strain_grad, node_ptr, state, fmax, sm
                                    ptr(state.n_pos), ptr(state.steps), ptr(state.done), ptr(state.fmax_seen), ptr(state.smax_seen),
                                    int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
                                    float(c["dt_max"]), float(c["maxstep"]), float(c["max_deform"]), stream()), "mdl_fire_cell_step")
+    return state
+
+
+# ------------------------------------------------------------------------------------------------
+# Nudged elastic band: the band force of every image (csrc/neb.hip), then FIRE over whole bands — the band mode of mdl_fire_step
+# ------------------------------------------------------------------------------------------------
+def neb_state(image_ptr, band_ptr, fixed=None, dt=0.1, alpha=0.1):
+    """A fresh NebState for I images (the structures of a batch: image_ptr [I + 1] int64, their node_ptr) grouped into B bands
+    (band_ptr [B + 1] int64: band b owns the consecutive images band_ptr[b] .. band_ptr[b + 1] - 1; its first and last image are
+    its fixed end points), device tensors.  fixed [N] uint8 / bool or None: atoms that do not move in any image they are in.
+    The layout is validated ONCE, here, with a host read: image_ptr starts at 0 and does not decrease, band_ptr does not decrease
+    and spans 0 .. I, and the images of a band have equal atom counts."""
+    who = "neb_state"
+    require_hip(image_ptr, band_ptr, fixed)
+    for name, t in (("image_ptr", image_ptr), ("band_ptr", band_ptr)):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 1:
+            raise MdlError("%s: %s must be a 1-d int64 tensor with at least one entry" % (who, name))
+    if band_ptr.device != image_ptr.device:
+        raise MdlError("%s: image_ptr and band_ptr must be on one device" % who)
+    dev, I, B = image_ptr.device, image_ptr.numel() - 1, band_ptr.numel() - 1
+    ip, bp = image_ptr.detach().cpu(), band_ptr.detach().cpu()               # the one host read
+    if int(ip[0]) != 0 or bool((ip[1:] < ip[:-1]).any()):
+        raise MdlError("%s: image_ptr must start at 0 and be non-decreasing" % who)
+    if int(bp[0]) != 0 or int(bp[-1]) != I or bool((bp[1:] < bp[:-1]).any()):
+        raise MdlError("%s: band_ptr must be non-decreasing and span 0 .. I = %d (got %d .. %d)" % (who, I, int(bp[0]), int(bp[-1])))
+    N, counts = int(ip[-1]), ip[1:] - ip[:-1]
+    ends = torch.zeros(N, dtype=torch.bool)
+    for b in range(B):
+        i0, i1 = int(bp[b]), int(bp[b + 1])
+        if i1 > i0:
+            if bool((counts[i0:i1] != counts[i0]).any()):
+                raise MdlError("%s: the images of band %d have unequal atom counts %s" % (who, b, counts[i0:i1].tolist()))
+            for s in (i0, i1 - 1):
+                ends[int(ip[s]):int(ip[s + 1])] = True
+    mask = ends.to(dev)
+    if fixed is not None:
+        if fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
+            raise MdlError("%s: fixed must be [N] uint8 or bool with N = %d (got %s %s)" % (who, N, tuple(fixed.shape), fixed.dtype))
+        if fixed.device != dev:
+            raise MdlError("%s: fixed must be on the device of image_ptr" % who)
+        mask = mask | (fixed != 0)
+    base = fire_state(B, dt, alpha, dev)
+    return NebState(*[getattr(base, k) for k in FireState.__slots__], image_ptr.detach().clone().contiguous(),
+                    band_ptr.detach().clone().contiguous(), ip[bp].to(dev), mask.to(torch.uint8),
+                    torch.full((B,), -1, dtype=torch.int32, device=dev), torch.zeros(I, dtype=torch.float64, device=dev),
+                    torch.zeros(I, dtype=torch.float64, device=dev), torch.zeros((N, 3), dtype=torch.float32, device=dev))
+
+
+def neb_step(pos, vel, force, energy, cell, pbc, state, fmax, spring=1.0, climb=True, **constants):
+    """One nudged-elastic-band step of every band of a batch, in place, in ONE call: the band force of every image — improved
+    tangent, springs along it, the climbing image turned uphill (include/mdl_hip.h, mdl_fire_step, band mode) — and then the FIRE
+    update of fire_step over whole BANDS: one time step, one alpha, one F.v and one convergence latch per band; maxstep bounds the
+    norm of the band's whole displacement.
+      pos, vel [N, 3] float64 (updated in place: contiguous tensors), force [N, 3] float32 (the TRUE force) and energy [I] float32
+      of the images, cell [I, 3, 3] float64 and pbc [I] int32 (bit a: axis a periodic; what ForceField.cell / .pbc hold), state a
+      NebState (ops.neb_state; updated in place), fmax, spring a number or a [B] float64 tensor each, climb a number / bool or a
+      [B] tensor (non-zero: the band's interior image of largest energy climbs), constants: any of FIRE_CONSTANTS.
+    A band is converged once the largest per-atom |F_band| over all its images is below its fmax; it is then left alone as
+    fire_step leaves a structure.  state.band_force, .tangent_force, .seg_len and .climber are written for every band, converged
+    or not.  Displacements between neighbouring images are wrapped to their minimum image in the cell of the middle one: exact
+    while no atom moves half a cell height or more between neighbours — the caller's condition.  Two stream-ordered launches, no
+    host synchronisation, no atomics: two calls from the same inputs give the same bits, a band alone or in any batch.
+    Returns state."""
+    who = "neb_step"
+    if not isinstance(state, NebState):
+        raise MdlError("%s: state must be an ops.NebState (ops.neb_state)" % who)
+    require_hip(energy, cell, pbc)
+    c, N, B, (fmax, spring), fixed = _fire_args(who, pos, vel, force, state.band_node_ptr, state, (("fmax", fmax), ("spring", spring)),
+                                                state.fixed, constants)
+    I = state.image_ptr.numel() - 1
+    for k, dt_, shape in _NEB_FIELDS:
+        t = getattr(state, k)
+        if t.dtype != dt_ or tuple(t.shape) != shape(N, I, B) or not t.is_contiguous():
+            raise MdlError("%s: state.%s must be a contiguous %s %s tensor (got %s %s)" % (who, k, list(shape(N, I, B)), dt_, tuple(t.shape), t.dtype))
+    for name, t, dt_, shape in (("energy", energy, torch.float32, (I,)), ("cell", cell, torch.float64, (I, 3, 3)), ("pbc", pbc, torch.int32, (I,))):
+        if t.dtype != dt_ or tuple(t.shape) != shape:
+            raise MdlError("%s: %s must be %s %s with I = %d images (got %s %s)" % (who, name, list(shape), dt_, I, tuple(t.shape), t.dtype))
+    if torch.is_tensor(climb):
+        if tuple(climb.shape) != (B,):
+            raise MdlError("%s: climb must be a number or a [B] tensor with B = %d (got %s)" % (who, B, tuple(climb.shape)))
+        require_hip(climb)
+        climb = (climb != 0).to(torch.uint8)
+    else:
+        climb = torch.full((B,), 1 if climb else 0, dtype=torch.uint8, device=pos.device)
+    if any(t.device != pos.device for t in (energy, cell, pbc, climb, state.image_ptr, state.band_ptr, state.band_force)):
+        raise MdlError("%s: pos, energy, cell, pbc, climb and the state must be on one device" % who)
+    check(lib().mdl_fire_step(ptr(pos), ptr(vel), ptr(force.contiguous()), ptr(fixed), ptr(state.band_node_ptr), N, B, ptr(fmax),
+                              ptr(state.dt), ptr(state.alpha), ptr(state.n_pos), ptr(state.steps), ptr(state.done), ptr(state.fmax_seen),
+                              int(c["n_min"]), float(c["f_inc"]), float(c["f_dec"]), float(c["alpha_start"]), float(c["f_alpha"]),
+                              float(c["dt_max"]), float(c["maxstep"]), ptr(state.image_ptr), ptr(state.band_ptr), I,
+                              ptr(energy.contiguous()), ptr(cell.contiguous()), ptr(pbc.contiguous()), ptr(spring), ptr(climb),
+                              ptr(state.band_force), ptr(state.tangent_force), ptr(state.seg_len), ptr(state.climber), stream()),
+          "mdl_fire_step")
     return state
 
 
