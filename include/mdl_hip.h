@@ -782,10 +782,38 @@ int mdl_fire_cell_step(double* pos, double* cell, double* scaled, double* deform
  * xi_x, xi_y = sqrt(-2 ln u0) (cos, sin)(2 pi u1), xi_z = sqrt(-2 ln u2) cos(2 pi u3).  Nothing outside structure b enters its
  * result: alone or in any batch it gets the same bits from the same seed.
  * Sums by wave shuffles, then the waves through LDS in wave order; lane 0 alone reads and writes what is per structure: no atomics,
- * bitwise repeatable.  Caller owns every buffer; no allocation, no synchronisation.  B == 0 or N == 0 returns 0 without a launch. */
+ * bitwise repeatable.  Caller owns every buffer; no allocation, no synchronisation.  B == 0 or N == 0 returns 0 without a launch.
+ *
+ * The cell mode: cell != NULL.  cell == NULL is the plain mode above; the other cell-mode arguments are then not looked at.  In the
+ * cell mode strain_grad, pressure, baro_rate, volume and press must be non-NULL and max_strain > 0: MDL_E_ARG otherwise.  It adds an
+ * isotropic barostat at constant pressure to the step: stochastic cell rescaling (Bernetti & Bussi, J. Chem. Phys. 153, 114107
+ * (2020)) in eps = ln V, inside the same call, still ONE launch and one force evaluation per step.
+ *   cell [B, 3, 3] fp64 (rows are lattice vectors), in / out;  strain_grad [B, 3, 3] fp32: S = dE/d eps of the structure, NOT
+ *   divided by the volume (only its diagonal is read: the barostat is isotropic);  pressure [B] fp64: the target P0, any sign;
+ *   baro_rate [B] fp64 >= 0: rate = compressibility / tau_p, in 1 / (pressure x time);  read.  volume, press [B] fp64: written.
+ * Structure b, items as above:
+ *   1. - 2. as above; 3. ekin as above, then V = |det cell[b]| and the instantaneous pressure P_int = (2 ekin - tr S) / (3 V) with
+ *      2 ekin = sum m |v|^2.  volume[b] = V and press[b] = P_int are written for every running structure, the closing call included;
+ *      both are NaN where !(V > 0).
+ *   4. as above: the closing call does not touch the cell.
+ *   4a. baro_rate[b] > 0: the barostat's step  d eps = -rate (P0 - P_int) dt + sqrt(2 kT rate dt / V) xi_V.  kT == 0 draws no
+ *      number: the Berendsen limit.  If !(V > 0) or !(|d eps| <= max_strain) — a NaN does not pass —: the v of item 2 and ekin are
+ *      written, status = 3 (refused by the strain guard), positions and cell keep their bits.  Else s = exp(d eps / 3), x_s = s x
+ *      for EVERY atom and v_s = v / s for the free ones: fixed atoms ride with the cell and keep zero velocity.
+ *   5. - 6. as above from (x_s, v_s) with the forces given — those of the UNSCALED positions: first-order splitting, as in the
+ *      paper's own integrator.  The guard measures |x'' - x_s|, the thermal motion; the affine part is bounded by max_strain.  A
+ *      refusal (status 2) writes the unscaled v of item 2 and ekin; positions and cell keep their bits.
+ *   7. else x'' and v'' are written (fixed atoms: x_s and 0), cell[b] <- s cell[b], steps += 1.
+ *   baro_rate[b] == 0: the structure runs the statements of the plain mode: pos, vel, steps, status and ekin get the bits of the
+ *      plain mode on the same inputs (one kernel body, contraction off, every fma written out), and its cell is not written.
+ * xi_V: the first normal number (xi_x above) of counter (0, 0, steps[b] before the increment, tag 2) under the structure's key.
+ * Volume, pressure, d eps and s are formed by every lane from the same numbers, behind the reduction that gives ekin; n_bad on the
+ * scaled candidate is a second reduction.  Lane 0 alone reads and writes cell, volume and press. */
 int mdl_md_step(double* pos, double* vel, const float* force, const double* mass, const uint8_t* fixed, const int64_t* node_ptr,
                 int64_t N, int64_t B, const double* dt, const double* gamma, const double* kT, const int64_t* seed,
-                const int32_t* n_steps, int32_t* steps, int32_t* status, double* ekin, double max_disp, mdlStream_t stream);
+                const int32_t* n_steps, int32_t* steps, int32_t* status, double* ekin, double max_disp, double* cell,
+                const float* strain_grad, const double* pressure, const double* baro_rate, double* volume, double* press,
+                double max_strain, mdlStream_t stream);
 
 /* mdl_md_velocities: Maxwell-Boltzmann velocities, vel [N, 3] fp64 written: v_i = sqrt(kT[b] / m_i) xi_i with the noise of
  * mdl_md_step at tag 1 and step word 0; fixed atoms get 0.  zero_momentum != 0 and at least two free atoms in the structure:

@@ -150,7 +150,7 @@ PROTOTYPES = {
     # ... maxstep | the band mode: image_ptr, band_ptr, I, nine operands of the band force | stream
     "mdl_fire_step": (_i32, [_vp] * 5 + [_i64, _i64] + [_vp] * 7 + [_i32] + [ctypes.c_double] * 6 + [_vp, _vp, _i64] + [_vp] * 9 + [_vp]),
     "mdl_fire_cell_step": (_i32, [_vp] * 13 + [_i64, _i64] + [_vp] * 9 + [_i32] + [ctypes.c_double] * 7 + [_vp]),
-    "mdl_md_step": (_i32, [_vp] * 6 + [_i64, _i64] + [_vp] * 8 + [ctypes.c_double, _vp]),
+    "mdl_md_step": (_i32, [_vp] * 6 + [_i64, _i64] + [_vp] * 8 + [ctypes.c_double] + [_vp] * 6 + [ctypes.c_double, _vp]),
     "mdl_md_velocities": (_i32, [_vp] * 4 + [_i64, _i64, _vp, _vp, _i32, _vp]),
 }
 

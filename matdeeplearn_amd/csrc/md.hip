@@ -10,6 +10,11 @@
 //                      pass 2: the branch all lanes take from those two sums: the closing call (steps == n_steps) and a refused
 //                              step store the v of pass 1, an accepted step the candidate, formed again by the same statements.
 //                      An atom's row is read and written by one lane only, so the update is in place.
+//                      The cell mode (cell != NULL) adds an isotropic barostat, stochastic cell rescaling (Bernetti & Bussi,
+//                      J. Chem. Phys. 153, 114107 (2020)) in eps = ln V: behind the sum for the kinetic energy every lane forms
+//                      volume, pressure and the strain d eps of the step from the same numbers; positions and cell are scaled by
+//                      s = exp(d eps / 3), velocities by 1 / s, and B A O A starts from the scaled pair.  The forces are those of
+//                      the UNSCALED positions: first-order splitting, as in the paper's own integrator.
 //   mdl_md_velocities  Maxwell-Boltzmann velocities from the same noise, the centre-of-mass velocity of the free atoms removed.
 // Noise: Philox4x32-10 (Salmon et al., SC'11) keyed by the structure's seed and counted by (atom within the structure, 0, step,
 // tag), so a structure's random numbers do not depend on the batch it is in, on the launch or on the process; Box-Muller on
@@ -23,7 +28,7 @@ namespace mdl {
 namespace {
 
 constexpr int MD_THREADS = STRUCT_THREADS;
-constexpr uint32_t MD_TAG_THERMOSTAT = 0, MD_TAG_VELOCITIES = 1;
+constexpr uint32_t MD_TAG_THERMOSTAT = 0, MD_TAG_VELOCITIES = 1, MD_TAG_BAROSTAT = 2;
 
 // Philox4x32-10: counter c[4], key (k0, k1) -> c
 __device__ __forceinline__ void philox4x32_10(uint32_t* c, uint32_t k0, uint32_t k1) {
@@ -68,6 +73,11 @@ struct MdArgs {
     const int32_t* n_steps;
     int32_t *steps, *status;
     double* ekin;
+    // the cell mode
+    double* cell;
+    const float* strain_grad;
+    const double *pressure, *baro_rate;
+    double *volume, *press;
 };
 
 // what one atom needs of its structure
@@ -88,9 +98,10 @@ __device__ __forceinline__ void md_closed_velocity(const MdArgs& a, const MdStep
     }
 }
 
-// B A O A of free atom i from the v of item 2: x'' and v''; returns |x'' - x|
-__device__ __forceinline__ double md_candidate(const MdArgs& a, const MdStep& s, int64_t i, uint32_t atom, double m, const double* v,
-                                               double* xn, double* vn) {
+// B A O A of free atom i from the position x and the velocity v (the row of pos and the v of item 2; in the cell mode both scaled
+// by the barostat): x'' and v''; returns |x'' - x|
+__device__ __forceinline__ double md_candidate(const MdArgs& a, const MdStep& s, int64_t i, uint32_t atom, double m, const double* x,
+                                               const double* v, double* xn, double* vn) {
 #pragma clang fp contract(off)
     double xi[3] = {0.0, 0.0, 0.0}, sigma = 0.0;
     if (s.thermostat) {
@@ -100,22 +111,41 @@ __device__ __forceinline__ double md_candidate(const MdArgs& a, const MdStep& s,
     double d[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const double x = a.pos[i * 3 + k];
         const double v1 = __builtin_fma(s.h, (double)a.force[i * 3 + k] / m, v[k]);
-        const double x1 = __builtin_fma(s.h, v1, x);
+        const double x1 = __builtin_fma(s.h, v1, x[k]);
         vn[k] = s.thermostat ? __builtin_fma(sigma, xi[k], s.c1 * v1) : v1;
         xn[k] = __builtin_fma(s.h, vn[k], x1);
-        d[k] = xn[k] - x;
+        d[k] = xn[k] - x[k];
     }
     return sqrt(__builtin_fma(d[2], d[2], __builtin_fma(d[0], d[0], d[1] * d[1])));
 }
 
-__global__ __launch_bounds__(MD_THREADS) void md_step_kernel(MdArgs a, double max_disp) {
+// what the candidate of free atom i starts from: its row of pos and the v of item 2, or — where the barostat acts — s x and v / s
+__device__ __forceinline__ void md_start(const MdArgs& a, int64_t i, bool baro, double sc, const double* v, double* xs, double* vs) {
 #pragma clang fp contract(off)
-    __shared__ double red[STRUCT_WAVES][2];
-    __shared__ double st_d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = a.pos[i * 3 + k];
+        xs[k] = baro ? sc * x : x;
+        vs[k] = baro ? v[k] / sc : v[k];
+    }
+}
+
+// ONE kernel body, instantiated twice.
+// CELL = false: the atoms alone (include/mdl_hip.h, mdl_md_step with cell == NULL): one reduction carries both sums, and no cell
+// pointer is touched.
+// CELL = true: the cell mode.  The barostat needs the kinetic energy before the candidate can be formed, so the sums are two
+// reductions: ekin, then — behind the barostat's decision, which every lane takes from the same numbers — n_bad on the scaled
+// candidate.  A structure with rate == 0 runs the statements of CELL = false on the same operands: the same bits.
+template <bool CELL>
+__global__ __launch_bounds__(MD_THREADS) void md_step_kernel(MdArgs a, double max_disp, double max_strain) {
+#pragma clang fp contract(off)
+    __shared__ double red[STRUCT_WAVES][CELL ? 1 : 2];
+    __shared__ double red2[STRUCT_WAVES][1];                   // CELL only
+    __shared__ double st_d[5];
     __shared__ int64_t st_seed;
     __shared__ int32_t st_i[3];
+    __shared__ double m_C[9], m_S[3];                          // CELL only: the cell and the diagonal of dE/d eps
     const int64_t b = blockIdx.x;
     int64_t n0 = a.node_ptr[b], n1 = a.node_ptr[b + 1];
     n0 = n0 < 0 ? 0 : (n0 > a.N ? a.N : n0);
@@ -128,6 +158,12 @@ __global__ __launch_bounds__(MD_THREADS) void md_step_kernel(MdArgs a, double ma
         st_i[0] = a.n_steps[b];
         st_i[1] = a.steps[b];
         st_i[2] = a.status[b];
+        if constexpr (CELL) {
+            st_d[3] = a.pressure[b];
+            st_d[4] = a.baro_rate[b];
+            for (int k = 0; k < 9; ++k) m_C[k] = a.cell[b * 9 + k];
+            for (int k = 0; k < 3; ++k) m_S[k] = (double)a.strain_grad[b * 9 + 4 * k];
+        }
     }
     __syncthreads();
     if (st_i[2] != 0) return;                                  // stopped before: nothing of the structure is written (uniform)
@@ -149,7 +185,7 @@ __global__ __launch_bounds__(MD_THREADS) void md_step_kernel(MdArgs a, double ma
     }
     const uint8_t* fixed = a.fixed;
 
-    // pass 1: acc = (sum m |v|^2, the number of free atoms whose candidate is not within max_disp)
+    // pass 1: acc = (sum m |v|^2, the number of free atoms whose candidate is not within max_disp); CELL: the first sum alone
     double acc[2] = {0.0, 0.0};
     for (int64_t i = n0 + threadIdx.x; i < n1; i += MD_THREADS) {
         if (fixed && fixed[i]) continue;
@@ -157,36 +193,85 @@ __global__ __launch_bounds__(MD_THREADS) void md_step_kernel(MdArgs a, double ma
         double v[3], xn[3], vn[3];
         md_closed_velocity(a, s, i, m, v);
         acc[0] += m * __builtin_fma(v[2], v[2], __builtin_fma(v[0], v[0], v[1] * v[1]));
-        if (!closing) acc[1] += md_candidate(a, s, i, (uint32_t)(i - n0), m, v, xn, vn) <= max_disp ? 0.0 : 1.0;
+        if constexpr (!CELL)
+            if (!closing) acc[1] += md_candidate(a, s, i, (uint32_t)(i - n0), m, a.pos + i * 3, v, xn, vn) <= max_disp ? 0.0 : 1.0;
     }
-    block_reduce<2, 2>(acc, red);
-    const bool accepted = !closing && !(acc[1] > 0.0);
+    block_reduce<CELL ? 1 : 2, CELL ? 1 : 2>(acc, red);
 
-    // pass 2: the velocities (and, of an accepted step, the positions); a fixed atom's velocity is written as zero
+    // CELL: volume and pressure, the barostat's strain and its guard — every lane from the same numbers
+    bool baro = false, strained = false;
+    double sc = 1.0, C[9];
+    if constexpr (CELL) {
+        double adj[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) C[k] = m_C[k];
+        const double V = fabs(adjugate3(C, adj));
+        const bool has_volume = V > 0.0;                       // (a NaN has none)
+        const double P = has_volume ? (acc[0] - (m_S[0] + m_S[1] + m_S[2])) / (3.0 * V) : __builtin_nan("");
+        if (threadIdx.x == 0) {
+            a.volume[b] = has_volume ? V : __builtin_nan("");
+            a.press[b] = P;
+        }
+        const double rate = st_d[4];
+        baro = !closing && rate > 0.0;
+        if (baro) {
+            double de = -((rate * (st_d[3] - P)) * dt);
+            if (s.kT > 0.0) {
+                double xi[3];
+                md_noise(0u, s.step, MD_TAG_BAROSTAT, s.seed, xi);
+                de = __builtin_fma(sqrt(2.0 * s.kT * rate * dt / V), xi[0], de);
+            }
+            strained = !has_volume || !(fabs(de) <= max_strain);                    // (a NaN does not pass)
+            if (!strained) sc = exp(de / 3.0);
+        }
+        if (!closing && !strained) {                           // uniform
+            // pass 1b: the number of free atoms whose candidate, from s x and v / s, is not within max_disp of s x
+            for (int64_t i = n0 + threadIdx.x; i < n1; i += MD_THREADS) {
+                if (fixed && fixed[i]) continue;
+                const double m = a.mass[i];
+                double v[3], xs[3], vs[3], xn[3], vn[3];
+                md_closed_velocity(a, s, i, m, v);
+                md_start(a, i, baro, sc, v, xs, vs);
+                acc[1] += md_candidate(a, s, i, (uint32_t)(i - n0), m, xs, vs, xn, vn) <= max_disp ? 0.0 : 1.0;
+            }
+            block_reduce<1, 1>(acc + 1, red2);
+        }
+    }
+    const bool accepted = !closing && !strained && !(acc[1] > 0.0);
+
+    // pass 2: the velocities (and, of an accepted step, the positions); a fixed atom's velocity is written as zero, and where the
+    // barostat acts its position rides with the cell
     for (int64_t i = n0 + threadIdx.x; i < n1; i += MD_THREADS) {
         double v[3] = {0.0, 0.0, 0.0};
         if (!(fixed && fixed[i])) {
             const double m = a.mass[i];
             md_closed_velocity(a, s, i, m, v);
             if (accepted) {
-                double xn[3], vn[3];
-                md_candidate(a, s, i, (uint32_t)(i - n0), m, v, xn, vn);
+                double xs[3], vs[3], xn[3], vn[3];
+                md_start(a, i, baro, sc, v, xs, vs);
+                md_candidate(a, s, i, (uint32_t)(i - n0), m, xs, vs, xn, vn);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     a.pos[i * 3 + k] = xn[k];
                     v[k] = vn[k];
                 }
             }
+        } else if (CELL && accepted && baro) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.pos[i * 3 + k] = sc * a.pos[i * 3 + k];
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) a.vel[i * 3 + k] = v[k];
     }
     if (threadIdx.x == 0) {
         a.ekin[b] = 0.5 * acc[0];
-        if (accepted)
+        if (accepted) {
             a.steps[b] = steps + 1;
-        else
-            a.status[b] = closing ? 1 : 2;
+            if (CELL && baro)
+                for (int k = 0; k < 9; ++k) a.cell[b * 9 + k] = sc * C[k];
+        } else {
+            a.status[b] = closing ? 1 : (strained ? 3 : 2);
+        }
     }
 }
 
@@ -253,15 +338,24 @@ int md_check(const char* fn, int64_t N, int64_t B) {
 extern "C" int mdl_md_step(double* pos, double* vel, const float* force, const double* mass, const uint8_t* fixed,
                            const int64_t* node_ptr, int64_t N, int64_t B, const double* dt, const double* gamma, const double* kT,
                            const int64_t* seed, const int32_t* n_steps, int32_t* steps, int32_t* status, double* ekin, double max_disp,
-                           mdlStream_t stream) {
+                           double* cell, const float* strain_grad, const double* pressure, const double* baro_rate, double* volume,
+                           double* press, double max_strain, mdlStream_t stream) {
     using namespace mdl;
     if (const int err = md_check("mdl_md_step", N, B)) return err;
     MDL_REQUIRE(max_disp > 0.0, MDL_E_ARG, "mdl_md_step: max_disp must be > 0 (got %g)", max_disp);
+    if (cell) {                                                // the cell mode
+        MDL_REQUIRE(max_strain > 0.0, MDL_E_ARG, "mdl_md_step: cell mode: max_strain must be > 0 (got %g)", max_strain);
+        MDL_REQUIRE(strain_grad && pressure && baro_rate && volume && press, MDL_E_ARG, "mdl_md_step: cell mode: null pointer");
+    }
     if (B == 0 || N == 0) return MDL_OK;
     MDL_REQUIRE(pos && vel && force && mass && node_ptr && dt && gamma && kT && seed && n_steps && steps && status && ekin, MDL_E_ARG,
                 "mdl_md_step: null pointer");
-    const MdArgs a = {pos, vel, force, mass, fixed, node_ptr, N, dt, gamma, kT, seed, n_steps, steps, status, ekin};
-    hipLaunchKernelGGL(md_step_kernel, dim3((unsigned)B), dim3(MD_THREADS), 0, (hipStream_t)stream, a, max_disp);
+    const MdArgs a = {pos,  vel,  force,       mass,     fixed,     node_ptr, N,    dt, gamma, kT, seed, n_steps, steps, status,
+                      ekin, cell, strain_grad, pressure, baro_rate, volume,   press};
+    if (cell)
+        hipLaunchKernelGGL(md_step_kernel<true>, dim3((unsigned)B), dim3(MD_THREADS), 0, (hipStream_t)stream, a, max_disp, max_strain);
+    else
+        hipLaunchKernelGGL(md_step_kernel<false>, dim3((unsigned)B), dim3(MD_THREADS), 0, (hipStream_t)stream, a, max_disp, 0.0);
     return check_launch("mdl_md_step");
 }
 

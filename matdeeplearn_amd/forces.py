@@ -28,7 +28,8 @@ launch (ops.fire_step, csrc/relax.hip), every structure with its own time step a
 the cell with the atoms: the same update over the atoms' rows and the three rows of the deformation gradient, driven by the strain
 gradient of energy_forces_stress (ops.fire_cell_step), still one launch per step.  md follows the forces at a temperature: BAOAB,
 NVE or Langevin, one launch per step too (ops.md_step, csrc/md.hip), with counter-based noise, so a structure's trajectory is the
-same alone and in any batch.  neb finds the barrier between two minima: the images of nudged elastic bands are the structures of ONE
+same alone and in any batch; md_npt is md at a pressure: an isotropic barostat (stochastic cell rescaling), driven by the strain
+gradient, inside the same launch (ops.md_cell_step).  neb finds the barrier between two minima: the images of nudged elastic bands are the structures of ONE
 ForceField, the band force (improved tangent, springs, climbing image) of every image is one launch (csrc/neb.hip) and FIRE then
 moves every band as one object (ops.neb_step: the band mode of mdl_fire_step); interpolate_band makes a band from two end points."""
 import collections
@@ -638,7 +639,19 @@ def md(model, structs, dist_range, masses, dt, steps, kT=0.0, gamma=0.0, kT_init
     only where check_every ended the loop), epot_trace [steps + 1, B(, out)] fp32 and ekin_trace [steps + 1, B] float64 — row n:
     prediction and kinetic energy at the positions after n steps (NaN rows: evaluations not made) —, node_ptr), device tensors.
     With ops.deterministic() two calls return the same bits."""
-    who = "md"
+    ff, vel, state, (energy, f), (epot_trace, ekin_trace) = _md("md", model, structs, dist_range, masses, dt, steps, kT, gamma, kT_init, velocities,
+                                                                seed, fixed, rebuild_every, max_disp, check_every,
+                                                                (radius, max_neighbors, dictionary, output_index))
+    return MDResult(ff.positions, vel, energy, f, state.ekin, state.steps, state.status, epot_trace, ekin_trace, ff.node_ptr)
+
+
+def _md(who, model, structs, dist_range, masses, dt, steps, kT, gamma, kT_init, velocities, seed, fixed, rebuild_every, max_disp, check_every,
+        ff_args, baro=None):
+    """md and md_npt (`who`) behind their arguments: the checks, the ForceField, the velocities and the rebuild / evaluate / step
+    loop.  baro: None (ops.md_step on the forces alone), or md_npt's (pressure, rate, max_strain) as [B] host arrays and a number
+    (ops.md_cell_step on forces and strain gradient; the kernel writes ff.cell).  Returns (the ForceField, the velocities, the
+    state, what the last evaluation returned, the traces: prediction and state.ekin — with baro also state.volume and
+    state.pressure — at every evaluation)."""
     _accepted(model, dist_range)
     if model.training:
         raise ops.MdlError("%s: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
@@ -646,7 +659,7 @@ def md(model, structs, dist_range, masses, dt, steps, kT=0.0, gamma=0.0, kT_init
     steps, rebuild_every, check_every = int(steps), int(rebuild_every), int(check_every)
     if steps < 0 or rebuild_every < 0 or check_every < 0:
         raise ops.MdlError("%s: steps, rebuild_every and check_every must be >= 0" % who)
-    ff = ForceField(model, structs, dist_range, radius, max_neighbors, dictionary, output_index)
+    ff = ForceField(model, structs, dist_range, *ff_args)
     dev, N, B = ff.positions.device, ff.positions.shape[0], ff.node_ptr.numel() - 1
 
     def per_atom(v, what, tail, dtype):
@@ -668,19 +681,93 @@ def md(model, structs, dist_range, masses, dt, steps, kT=0.0, gamma=0.0, kT_init
         vel = ops.md_velocities(mass, ff.node_ptr, kT_t if kT_init is None else _per_structure(kT_init, B, dev, who, "kT_init"), seed_t, fixed)
     else:
         vel = per_atom(velocities, "velocities", (3,), torch.float64)
-    state = ops.md_state(B, dev)
+    if baro is None:
+        state, traced = ops.md_state(B, dev), ("ekin",)
+    else:
+        state, traced = ops.md_cell_state(B, dev), ("ekin", "volume", "pressure")
+        pressure_t, rate_t = [_per_structure(v, B, dev, who, name) for name, v in (("pressure", baro[0]), ("rate", baro[1]))]
     n_steps = torch.full((B,), steps, dtype=torch.int32, device=dev)
-    epot_trace = ekin_trace = None
+    traces = None
     for it in range(steps + 1):
         if it > 0 and rebuild_every > 0 and it % rebuild_every == 0:
             ff.rebuild()
-        energy, f = ff.evaluate()
-        ops.md_step(ff.positions, vel, f, mass, ff.node_ptr, state, dt_t, n_steps, gamma_t, kT_t, seed_t, fixed, max_disp)
-        if epot_trace is None:
-            epot_trace = torch.full((steps + 1,) + tuple(energy.shape), float("nan"), dtype=energy.dtype, device=dev)
-            ekin_trace = torch.full((steps + 1, B), float("nan"), dtype=torch.float64, device=dev)
-        epot_trace[it].copy_(energy)
-        ekin_trace[it].copy_(state.ekin)
+        if baro is None:
+            out = ff.evaluate()
+            ops.md_step(ff.positions, vel, out[1], mass, ff.node_ptr, state, dt_t, n_steps, gamma_t, kT_t, seed_t, fixed, max_disp)
+        else:
+            out = ff.evaluate(stress=True, volume_normalised=False)
+            ops.md_cell_step(ff.positions, vel, ff.cell, out[1], out[2], mass, ff.node_ptr, state, dt_t, n_steps, pressure_t, rate_t, gamma_t,
+                             kT_t, seed_t, fixed, max_disp, baro[2])
+        if traces is None:
+            traces = [torch.full((steps + 1,) + tuple(out[0].shape), float("nan"), dtype=out[0].dtype, device=dev)]
+            traces += [torch.full((steps + 1, B), float("nan"), dtype=torch.float64, device=dev) for _ in traced]
+        traces[0][it].copy_(out[0])
+        for t, k in zip(traces[1:], traced):
+            t[it].copy_(getattr(state, k))
         if check_every > 0 and (it + 1) % check_every == 0 and bool((state.status != 0).all()):
             break
-    return MDResult(ff.positions, vel, energy, f, state.ekin, state.steps, state.status, epot_trace, ekin_trace, ff.node_ptr)
+    return ff, vel, state, out[:2], traces
+
+
+# eV / A^3 per GPa: pressure = 0.1 * GPA is a kilobar, compressibility = 1 / (100 * GPA) that of a bulk modulus of 100 GPa
+GPA = 1e9 * 1e-30 / _E
+
+NPTResult = collections.namedtuple("NPTResult", "positions velocities cell energy forces ekin volume pressure steps status epot_trace "
+                                                "ekin_trace volume_trace pressure_trace node_ptr")
+
+
+def md_npt(model, structs, dist_range, masses, dt, steps, pressure, tau_p, compressibility, kT=0.0, gamma=0.0, kT_init=None, velocities=None,
+           seed=0, fixed=None, rebuild_every=1, max_disp=0.5, max_strain=0.03, check_every=0, radius=8.0, max_neighbors=12, dictionary=None,
+           output_index=None):
+    """md at constant pressure: the same loop with an isotropic barostat inside the integrator's launch (ops.md_cell_step) —
+    stochastic cell rescaling (Bernetti & Bussi, J. Chem. Phys. 153, 114107 (2020)) in eps = ln V, driven by the strain gradient
+    that the backward for the forces already forms.  With gamma > 0 and kT > 0 it samples the isothermal-isobaric ensemble (to
+    first order in dt: the forces of a step are those of the unscaled positions); with kT = 0 it is the Berendsen barostat.
+
+    model, structs, dist_range, masses, dt, steps, kT, gamma, kT_init, velocities, seed, fixed, rebuild_every, max_disp,
+    check_every, radius, max_neighbors, dictionary, output_index   as md
+    pressure      the target pressure, any sign, a number or one per structure, in the model's energy unit per cubic Angstrom
+                  (pressure = 1.0 * GPA is one gigapascal for a model trained on eV)
+    tau_p, compressibility   > 0, a number or one per structure each: the barostat's relaxation time and the (estimated) isothermal
+                  compressibility, 1 / pressure; only their ratio enters.  tau_p = math.inf switches the barostat of that structure
+                  off: it gets the bits of md, and its cell comes back as it went in.  A finite tau_p on a structure that is not
+                  periodic along all three axes raises MdlError
+    max_strain    the barostat's guard: a step that would change ln V by more than this (or whose cell has no volume) is not made;
+                  the structure stops at its last geometry with status 3.  0.03 is a 1 % linear change per step; max_disp then
+                  bounds the thermal motion alone
+
+    Returns NPTResult(positions, velocities [N, 3] float64, cell [B, 3, 3] float64, energy and forces [N, 3] fp32 at that geometry,
+    ekin, volume, pressure [B] float64 (the instantaneous pressure (2 ekin - tr dE/d eps) / (3 volume) there), steps, status [B]
+    int32 (1 finished, 2 stopped by max_disp, 3 stopped by max_strain, 0 still running), epot_trace [steps + 1, B(, out)] fp32,
+    ekin_trace, volume_trace, pressure_trace [steps + 1, B] float64, node_ptr), device tensors.  No host read beyond md's.  With
+    ops.deterministic() two calls return the same bits."""
+    who = "md_npt"
+    p = _packed(structs)
+    B = len(_host(p["node_ptr"], np.int64)) - 1
+
+    def per_structure(v, what, positive):
+        t = _host(v, np.float64)
+        if t.ndim == 0:
+            t = np.full(B, float(t))
+        if t.shape != (B,):
+            raise ops.MdlError("%s: %s must be a number or one value per structure, [%d] (got %s)" % (who, what, B, t.shape))
+        if positive and not (t > 0).all():                     # (a NaN is not)
+            raise ops.MdlError("%s: %s must be > 0" % (who, what))
+        return t
+
+    tau, kappa = per_structure(tau_p, "tau_p", True), per_structure(compressibility, "compressibility", True)
+    press = per_structure(pressure, "pressure", False)
+    if not np.isfinite(kappa).all() or not np.isfinite(press).all():
+        raise ops.MdlError("%s: compressibility and pressure must be finite" % who)
+    if not float(max_strain) > 0.0:
+        raise ops.MdlError("%s: max_strain must be > 0 (got %r)" % (who, max_strain))
+    rate = np.where(np.isinf(tau), 0.0, kappa / tau)
+    open_ = (_host(p["pbc"], np.int32) & 7) != 7
+    if (open_ & (rate > 0)).any():
+        raise ops.MdlError("%s: structures %s are not periodic along all three axes: they have no pressure (tau_p = math.inf switches "
+                           "their barostat off)" % (who, np.nonzero(open_ & (rate > 0))[0].tolist()))
+    ff, vel, state, (energy, f), (epot_trace, ekin_trace, volume_trace, pressure_trace) = _md(
+        who, model, p, dist_range, masses, dt, steps, kT, gamma, kT_init, velocities, seed, fixed, rebuild_every, max_disp, check_every,
+        (radius, max_neighbors, dictionary, output_index), (press, rate, float(max_strain)))
+    return NPTResult(ff.positions, vel, ff.cell, energy, f, state.ekin, state.volume, state.pressure, state.steps, state.status, epot_trace,
+                     ekin_trace, volume_trace, pressure_trace, ff.node_ptr)

@@ -3010,13 +3010,14 @@ def md_state(B, device=None):
 
 # per-structure operand -> (dtype, its range: ">" above zero, ">=" not below, None any value)
 _MD_PER_STRUCTURE = {"dt": (torch.float64, ">"), "gamma": (torch.float64, ">="), "kT": (torch.float64, ">="),
-                     "n_steps": (torch.int32, ">="), "seed": (torch.int64, None)}
+                     "n_steps": (torch.int32, ">="), "seed": (torch.int64, None), "pressure": (torch.float64, None),
+                     "rate": (torch.float64, ">=")}
 
 
 def _md_numbers(who, values):
     """the range of every operand given as a plain number — before a device or the library is asked for anything"""
     for name, v in values:
-        rng = ">" if name == "max_disp" else _MD_PER_STRUCTURE[name][1]
+        rng = ">" if name in ("max_disp", "max_strain") else _MD_PER_STRUCTURE[name][1]
         if torch.is_tensor(v) or rng is None:
             continue
         if not (float(v) > 0.0 if rng == ">" else float(v) >= 0.0):           # (a NaN is neither)
@@ -3086,29 +3087,98 @@ def md_step(pos, vel, force, mass, node_ptr, state, dt, n_steps, gamma=0.0, kT=0
     guard are stated in include/mdl_hip.h (mdl_md_step).  No atomics: two calls from the same inputs give the same bits.  No host
     synchronisation, except that the values of mass and of a tensor-valued dt, gamma, kT or n_steps are checked once per tensor (the
     state remembers which it has seen).  Returns state."""
-    who = "md_step"
-    if not isinstance(state, MDState):
-        raise MdlError("%s: state must be an ops.MDState (ops.md_state)" % who)
+    return _md_step("md_step", pos, vel, force, mass, node_ptr, state, dt, n_steps, gamma, kT, seed, fixed, max_disp)
+
+
+def _md_step(who, pos, vel, force, mass, node_ptr, state, dt, n_steps, gamma, kT, seed, fixed, max_disp, baro=None):
+    """md_step and md_cell_step (`who`) behind their arguments: the checks and the one launch.  baro: None, or md_cell_step's (cell,
+    strain_grad, pressure, rate, max_strain): the cell mode of mdl_md_step."""
+    state_type, maker = (MDState, "md_state") if baro is None else (MDCellState, "md_cell_state")
+    if not isinstance(state, state_type):
+        raise MdlError("%s: state must be an ops.%s (ops.%s)" % (who, state_type.__name__, maker))
     per = (("dt", dt), ("gamma", gamma), ("kT", kT), ("seed", seed), ("n_steps", n_steps))
-    _md_numbers(who, per + (("max_disp", max_disp),))
-    require_hip(pos, vel, force, state.steps, state.status, state.ekin)
+    fields = (("steps", torch.int32), ("status", torch.int32), ("ekin", torch.float64))
+    cell = strain_grad = None
+    if baro is not None:
+        cell, strain_grad, pressure, rate, max_strain = baro
+        per += (("pressure", pressure), ("rate", rate))
+        fields += (("volume", torch.float64), ("pressure", torch.float64))
+    _md_numbers(who, per + (("max_disp", max_disp),) + ((("max_strain", max_strain),) if baro is not None else ()))
+    if baro is not None:                                       # shapes that need no device to be wrong
+        Bc = node_ptr.numel() - 1 if torch.is_tensor(node_ptr) else -1
+        if not torch.is_tensor(cell) or cell.dtype != torch.float64 or tuple(cell.shape) != (Bc, 3, 3) or not cell.is_contiguous():
+            raise MdlError("%s: cell must be a contiguous [B, 3, 3] float64 tensor with B = %d (got %s %s)"
+                           % (who, Bc, tuple(getattr(cell, "shape", ())), getattr(cell, "dtype", type(cell))))
+        if not torch.is_tensor(strain_grad) or strain_grad.dtype != torch.float32 or tuple(strain_grad.shape) != (Bc, 3, 3):
+            raise MdlError("%s: strain_grad must be [B, 3, 3] float32 with B = %d (got %s %s)"
+                           % (who, Bc, tuple(getattr(strain_grad, "shape", ())), getattr(strain_grad, "dtype", type(strain_grad))))
+    state_tensors = [getattr(state, k) for k, _ in fields]
+    require_hip(pos, vel, force, cell, strain_grad, *state_tensors)
     N, B, fixed = _md_atoms(who, mass, node_ptr, fixed, state._checked)
     for name, t in (("pos", pos), ("vel", vel)):
         if t.dtype != torch.float64 or tuple(t.shape) != (N, 3) or not t.is_contiguous():
             raise MdlError("%s: %s must be a contiguous [N, 3] float64 tensor with N = %d (got %s %s)" % (who, name, N, tuple(t.shape), t.dtype))
     if force.dtype != torch.float32 or tuple(force.shape) != (N, 3):
         raise MdlError("%s: force must be [N, 3] float32 with N = %d (got %s %s)" % (who, N, tuple(force.shape), force.dtype))
-    for k, dt_ in (("steps", torch.int32), ("status", torch.int32), ("ekin", torch.float64)):
-        t = getattr(state, k)
+    for (k, dt_), t in zip(fields, state_tensors):
         if t.dtype != dt_ or tuple(t.shape) != (B,) or not t.is_contiguous():
             raise MdlError("%s: state.%s must be a contiguous [%d] %s tensor (got %s %s)" % (who, k, B, dt_, tuple(t.shape), t.dtype))
-    if any(t.device != pos.device for t in (vel, force, mass, state.steps, state.status, state.ekin)):
+    if any(t.device != pos.device for t in [vel, force, mass] + state_tensors + ([] if baro is None else [cell, strain_grad])):
         raise MdlError("%s: pos, the other tensors and the state must be on one device" % who)
-    dt, gamma, kT, seed, n_steps = _md_per_structure(who, per, B, pos.device, state._checked)
+    per = _md_per_structure(who, per, B, pos.device, state._checked)
+    dt, gamma, kT, seed, n_steps = per[:5]
+    if baro is None:
+        cell_args = [None] * 6 + [0.0]
+    else:
+        cell_args = [ptr(cell), ptr(strain_grad.contiguous()), ptr(per[5]), ptr(per[6]), ptr(state.volume), ptr(state.pressure), float(max_strain)]
     check(lib().mdl_md_step(ptr(pos), ptr(vel), ptr(force.contiguous()), ptr(mass), ptr(fixed), ptr(node_ptr.contiguous()), N, B, ptr(dt),
                             ptr(gamma), ptr(kT), ptr(seed), ptr(n_steps), ptr(state.steps), ptr(state.status), ptr(state.ekin),
-                            float(max_disp), stream()), "mdl_md_step")
+                            float(max_disp), *cell_args, stream()), "mdl_md_step")
     return state
+
+
+class MDCellState(MDState):
+    """Per-structure state of md_cell_step: the MDState fields (status 3: refused by the strain guard — the barostat would have
+    strained the cell by more than max_strain, or the cell has no volume) and what every call writes for a running structure:
+    volume, |det cell|, and pressure, the instantaneous (2 ekin - tr dE/d eps) / (3 volume), [B] float64, at the positions the
+    forces of the last call belong to; NaN where the cell has no volume."""
+
+    __slots__ = ("volume", "pressure")
+
+    def __init__(self, steps, status, ekin, volume, pressure):
+        MDState.__init__(self, steps, status, ekin)
+        self.volume, self.pressure = volume, pressure
+
+    def clone(self):
+        new = MDCellState(self.steps.clone(), self.status.clone(), self.ekin.clone(), self.volume.clone(), self.pressure.clone())
+        new._checked = dict(self._checked)
+        return new
+
+
+def md_cell_state(B, device=None):
+    """A fresh MDCellState of B structures: no step made, every structure running, volume and pressure not yet written (NaN)."""
+    base = md_state(B, device)
+    nan = lambda: torch.full((int(B),), float("nan"), dtype=torch.float64, device=base.ekin.device)
+    return MDCellState(base.steps, base.status, base.ekin, nan(), nan())
+
+
+def md_cell_step(pos, vel, cell, force, strain_grad, mass, node_ptr, state, dt, n_steps, pressure, rate, gamma=0.0, kT=0.0, seed=0, fixed=None,
+                 max_disp=0.5, max_strain=0.03):
+    """md_step at constant pressure: the same call with an isotropic barostat in it — stochastic cell rescaling (Bernetti & Bussi,
+    J. Chem. Phys. 153, 114107 (2020)) in eps = ln V —, for every structure of a batch, in place, still in ONE launch.
+      pos, vel, force, mass, node_ptr, dt, n_steps, gamma, kT, seed, fixed, max_disp   as md_step
+      cell [B, 3, 3] float64 (rows are lattice vectors; updated in place: a contiguous tensor), strain_grad [B, 3, 3] float32 (dE/d eps,
+      NOT divided by the volume: ForceField.evaluate(stress=True, volume_normalised=False)), state an MDCellState (ops.md_cell_state;
+      updated in place: volume and pressure are written for every running structure)
+      Per structure, a number or a [B] float64 tensor each: pressure (the target, any sign; in the energy unit per volume) and
+      rate >= 0 (compressibility / tau_p; 0: no barostat — the structure gets the bits of md_step and its cell is not written)
+      max_strain > 0: a step whose volume strain |d eps| would exceed it is refused as a whole (status 3, positions and cell kept to
+      the bit); the default 0.03 is a 1 % linear change per step.  max_disp then bounds the thermal motion alone.
+    With kT == 0 the barostat draws no number (the Berendsen limit).  The forces are those of the unscaled positions: first-order
+    splitting.  The update, the counter of the barostat's noise (tag 2) and the guards are stated in include/mdl_hip.h (mdl_md_step,
+    the cell mode).  No atomics, no host synchronisation beyond md_step's (a tensor-valued rate is checked once).  Returns state."""
+    return _md_step("md_cell_step", pos, vel, force, mass, node_ptr, state, dt, n_steps, gamma, kT, seed, fixed, max_disp,
+                    (cell, strain_grad, pressure, rate, max_strain))
 
 
 def md_velocities(mass, node_ptr, kT, seed=0, fixed=None, zero_momentum=True):

@@ -2,7 +2,7 @@
 """Molecular-dynamics step on the device: what one step of forces.md costs, phase by phase, and the integrator against the same
 update composed from torch ops.
 
-  python tools/bench_md.py [--model cgcnn|schnet] [--graphs 64,1024] [--dim 64] [--steps 20] [--repeats 5] [--seed 0]
+  python tools/bench_md.py [--model cgcnn|schnet] [--graphs 64,1024] [--dim 64] [--steps 20] [--repeats 5] [--seed 0] [--npt]
 
 Structures and model as tools/bench_relax.py takes them; masses uniform in [1, 4], dt = 1, Langevin at gamma = 0.05, kT = 2e-5 (an
 untrained model's forces are of order 1e-3 per A), Maxwell-Boltzmann velocities.  One JSON line per batch size:
@@ -14,7 +14,11 @@ untrained model's forces are of order 1e-3 per A), Maxwell-Boltzmann velocities.
                     structures), taking turns, best of repeats, on clones of one state
   max_pos_diff      largest difference between the positions md_nve_us and the composition without noise produce in that one step
   md_repeatable / torch_repeatable   whether 5 runs from the same inputs gave the same bits (torch.randn draws from the process's
-                    generator: the composed step repeats only if nothing else has drawn in between)"""
+                    generator: the composed step repeats only if nothing else has drawn in between)
+--npt adds the step of forces.md_npt from the same run (target pressure 0, rate = compressibility / tau_p = 30, max_strain = 0.03):
+  npt_rebuild_ms / npt_evaluate_ms / npt_md_ms / npt_stopped   the phases above with ForceField.evaluate(stress=True,
+                    volume_normalised=False) and ops.md_cell_step in the place of evaluate() and ops.md_step
+  md_cell_us        ops.md_cell_step alone on the forces and the strain gradient of the first step, taking turns with the others"""
 import argparse
 import json
 import os
@@ -31,6 +35,7 @@ from matdeeplearn_amd import forces, ops  # noqa: E402
 from matdeeplearn_amd.process import graph as pg  # noqa: E402
 
 MD = dict(dt=1.0, gamma=0.05, kT=2e-5, seed=0)
+NPT = dict(pressure=0.0, rate=30.0, max_strain=0.03)
 
 
 def torch_md_step(pos, vel, force, mass, batch, st, dt, n_steps, gamma, kT, max_disp):
@@ -67,32 +72,39 @@ def md_inputs(ff, seed):
     return mass, per(MD["dt"]), per(MD["gamma"]), per(MD["kT"]), torch.arange(B, dtype=torch.int64, device=dev) + MD["seed"]
 
 
-def md_phases(model, packed, steps, seed):
-    """one run, every step rebuilt: per-step means (ms) of the three phases, and how many structures the guard stopped"""
+def md_phases(model, packed, steps, seed, npt=False):
+    """one run, every step rebuilt: per-step means (ms) of the three phases, and how many structures a guard stopped; npt: the step
+    of forces.md_npt in the place of that of forces.md"""
     ff = forces.ForceField(model, packed, (0.0, 8.0))
     dev, B = ff.positions.device, ff.node_ptr.numel() - 1
     mass, dt, gamma, kT, keys = md_inputs(ff, seed)
     vel = ops.md_velocities(mass, ff.node_ptr, kT, keys)
-    state, n_steps = ops.md_state(B, dev), torch.full((B,), steps, dtype=torch.int32, device=dev)
+    state, n_steps = (ops.md_cell_state if npt else ops.md_state)(B, dev), torch.full((B,), steps, dtype=torch.int32, device=dev)
     marks = []
     for _ in range(steps):
         e = events(4)
         e[0].record()
         ff.rebuild()
         e[1].record()
-        _, f = ff.evaluate()
-        e[2].record()
-        ops.md_step(ff.positions, vel, f, mass, ff.node_ptr, state, dt, n_steps, gamma, kT, keys)
+        if npt:
+            _, f, strain = ff.evaluate(stress=True, volume_normalised=False)
+            e[2].record()
+            ops.md_cell_step(ff.positions, vel, ff.cell, f, strain, mass, ff.node_ptr, state, dt, n_steps, NPT["pressure"], NPT["rate"], gamma, kT,
+                             keys, max_strain=NPT["max_strain"])
+        else:
+            _, f = ff.evaluate()
+            e[2].record()
+            ops.md_step(ff.positions, vel, f, mass, ff.node_ptr, state, dt, n_steps, gamma, kT, keys)
         e[3].record()
         marks.append(e)
     torch.cuda.synchronize()
     return [sum(e[k].elapsed_time(e[k + 1]) for e in marks) / steps for k in range(3)], int((state.steps != steps).sum())
 
 
-def integrator_alone(model, packed, repeats, seed):
+def integrator_alone(model, packed, repeats, seed, npt=False):
     ff = forces.ForceField(model, packed, (0.0, 8.0))
     dev, B, N = ff.positions.device, ff.node_ptr.numel() - 1, ff.positions.shape[0]
-    _, f = ff.evaluate()
+    _, f, strain = ff.evaluate(stress=True, volume_normalised=False)
     batch = torch.repeat_interleave(torch.arange(B, device=dev), ff.node_ptr[1:] - ff.node_ptr[:-1], output_size=N)
     mass, dt, gamma, kT, keys = md_inputs(ff, seed)
     vel0 = ops.md_velocities(mass, ff.node_ptr, kT, keys)
@@ -115,6 +127,21 @@ def integrator_alone(model, packed, repeats, seed):
            lambda: timed(lambda p, v, s: ops.md_step(p, v, f, mass, ff.node_ptr, s, dt, n_steps, zero, kT, keys)),
            lambda: timed(lambda p, v, s: torch_md_step(p, v, f, mass, batch, s, dt, n_steps, gamma, kT, 0.5)),
            lambda: timed(lambda p, v, s: torch_md_step(p, v, f, mass, batch, s, dt, n_steps, torch.zeros_like(gamma), kT, 0.5)))
+    if npt:
+        cstate0 = ops.md_cell_state(B, dev)
+        cstate0._checked = dict(state0._checked)
+        cstate0.steps.fill_(3)
+
+        def timed_cell():
+            pos, vel, cell, st = ff.positions.clone(), vel0.clone(), ff.cell.clone(), cstate0.clone()
+            e = events(2)
+            e[0].record()
+            ops.md_cell_step(pos, vel, cell, f, strain, mass, ff.node_ptr, st, dt, n_steps, NPT["pressure"], NPT["rate"], gamma, kT, keys,
+                             max_strain=NPT["max_strain"])
+            e[1].record()
+            return e, pos
+
+        fns += (timed_cell,)
     for fn in fns:
         fn()
     best, outs = [None] * len(fns), [[] for _ in fns]
@@ -126,8 +153,11 @@ def integrator_alone(model, packed, repeats, seed):
             best[k] = t if best[k] is None else min(best[k], t)
             outs[k].append(pos)
     same = lambda ps: all(torch.equal(ps[0], p) for p in ps[1:5])
-    return {"md_us": round(best[0] * 1e3, 1), "md_nve_us": round(best[1] * 1e3, 1), "torch_us": round(best[2] * 1e3, 1),
-            "max_pos_diff": float((outs[1][0] - outs[3][0]).abs().max()), "md_repeatable": same(outs[0]), "torch_repeatable": same(outs[2])}
+    out = {"md_us": round(best[0] * 1e3, 1), "md_nve_us": round(best[1] * 1e3, 1), "torch_us": round(best[2] * 1e3, 1),
+           "max_pos_diff": float((outs[1][0] - outs[3][0]).abs().max()), "md_repeatable": same(outs[0]), "torch_repeatable": same(outs[2])}
+    if npt:
+        out.update(md_cell_us=round(best[4] * 1e3, 1), md_cell_repeatable=same(outs[4]))
+    return out
 
 
 def main():
@@ -138,6 +168,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--npt", action="store_true", help="add the step of forces.md_npt to every line")
     a = ap.parse_args()
     model = make_model(a, torch.device("cuda"))
     for B in [int(v) for v in a.graphs.split(",")]:
@@ -149,7 +180,14 @@ def main():
             best = t if best is None else [min(x, y) for x, y in zip(best, t)]
         line = {"model": a.model, "graphs": B, "atoms": int(packed["node_ptr"][-1]), "dim": a.dim, "steps": a.steps,
                 "rebuild_ms": round(best[0], 3), "evaluate_ms": round(best[1], 3), "md_ms": round(best[2], 4), "stopped": stopped}
-        line.update(integrator_alone(model, packed, a.repeats, a.seed))
+        if a.npt:
+            md_phases(model, packed, 2, a.seed, npt=True)
+            best = None
+            for _ in range(a.repeats):
+                t, stopped = md_phases(model, packed, a.steps, a.seed, npt=True)
+                best = t if best is None else [min(x, y) for x, y in zip(best, t)]
+            line.update(npt_rebuild_ms=round(best[0], 3), npt_evaluate_ms=round(best[1], 3), npt_md_ms=round(best[2], 4), npt_stopped=stopped)
+        line.update(integrator_alone(model, packed, a.repeats, a.seed, a.npt))
         print(json.dumps(line), flush=True)
 
 
