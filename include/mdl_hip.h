@@ -343,7 +343,14 @@ int mdl_loss_fwd_bwd_rows(const float* pred, const float* y, int64_t n, int64_t 
  * its atomics over them) followed by one [2, C] row pair of totals, which the *_apply call publishes
  * (sums + MDL_BN_REPLICAS*2*C: after bwd_apply = dbeta | dgamma).  `save` is [2, C] fp32 (mean | invstd) written
  * by mdl_bn_apply.
- * Supported: C a multiple of 8 (bf16) / 4 (fp32) with 256 % (C/W) == 0, C <= 256.
+ * Supported: N >= 1, C a multiple of 4, 4 <= C <= 256, fp32 or bf16 (else MDL_E_UNSUPP).  Rows are accessed as vectors of W
+ * elements — W = 8 for bf16 with C % 8 == 0, else 4 (fp32; bf16 C = 100: 8 bytes) — by blocks of 256 / (C/W) whole rows
+ * (C/W need not divide 256: C = 100 runs 250 threads).  x, y, dy and dx must be non-NULL and aligned to W elements, sums and
+ * save non-NULL: MDL_E_ARG with a message that names the tensor, before any launch.  gamma, beta, running_mean / running_var
+ * may be NULL (1, 0, no update).
+ * Accuracy of the shifted sums: they avoid the E[x^2] - E[x]^2 cancellation only while the first row is typical.  For a first
+ * row at distance d from a column's mean the variance is formed in fp32 as (s^2 + d^2) - d^2, so its rounding error scales
+ * with 1 + d^2 / s^2 (s^2 the column's variance): about 2^-22 (s^2 + d^2) absolute.
  *   stats:      copy[0] += sum(x - x[0,:]), copy[1] += sum((x - x[0,:])^2)   (shifted sums)
  *   apply:      y = (x - mean) * rsqrt(var_biased + eps) * gamma + beta; running_mean/var (unbiased) updated
  *               with `momentum` when non-NULL

@@ -243,12 +243,22 @@ static int bn_width(int C, int dtype) { return (dtype == MDL_BF16 && C % 8 == 0)
 // threads per block: a whole number of rows, each CG = C / W lanes wide
 static int bn_threads(int C, int W) { const int cg = C / W; return 256 / cg * cg; }
 
-static int bn_check(const char* name, int64_t N, int C, int dtype, const void* p) {
+// one operand of an entry point: `what` names it in the message
+struct BnPtr { const char* what; const void* p; bool rows; };
+
+// shape, dtype and every pointer the kernels touch, before any launch: the row tensors (x, y, dy, dx) are read and written as
+// vectors of W elements and must be aligned to them; sums and save are fp32 arrays read and written element by element
+template <size_t NP>
+static int bn_check(const char* name, int64_t N, int C, int dtype, const BnPtr (&ptrs)[NP]) {
     MDL_REQUIRE(dtype == MDL_F32 || dtype == MDL_BF16, MDL_E_UNSUPP, "%s: unsupported dtype %d", name, dtype);
     MDL_REQUIRE(N >= 1 && C >= 4 && C % 4 == 0 && C <= 256, MDL_E_UNSUPP,
                 "%s: need N>=1 and C a multiple of 4, C<=256 (got N=%lld C=%d)", name, (long long)N, C);
-    MDL_REQUIRE(p && reinterpret_cast<uintptr_t>(p) % (bn_width(C, dtype) * (dtype == MDL_BF16 ? 2 : 4)) == 0, MDL_E_ARG,
-                "%s: null or misaligned tensor", name);
+    const uintptr_t vec = (uintptr_t)bn_width(C, dtype) * (dtype == MDL_BF16 ? 2 : 4);
+    for (const BnPtr& t : ptrs) {
+        MDL_REQUIRE(t.p, MDL_E_ARG, "%s: %s is null", name, t.what);
+        MDL_REQUIRE(reinterpret_cast<uintptr_t>(t.p) % (t.rows ? vec : sizeof(float)) == 0, MDL_E_ARG,
+                    "%s: %s is not aligned to %d bytes", name, t.what, (int)(t.rows ? vec : sizeof(float)));
+    }
     return MDL_OK;
 }
 
@@ -268,7 +278,8 @@ extern "C" int mdl_bn_stats_n(const void* x, float* sums, int64_t N, int C, cons
     using namespace mdl;
     const bool det = (dtype & MDL_DETERMINISTIC) != 0;
     dtype &= MDL_DTYPE_MASK;
-    int rc = bn_check("mdl_bn_stats", N, C, dtype, x);
+    const BnPtr ptrs[] = {{"x", x, true}, {"sums", sums, false}};
+    int rc = bn_check("mdl_bn_stats", N, C, dtype, ptrs);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int W = bn_width(C, dtype);
@@ -284,7 +295,8 @@ extern "C" int mdl_bn_apply_n(const void* x, float* sums, const float* gamma, co
     using namespace mdl;
     const int shift_row = (dtype & MDL_BN_SHIFT_ROW) ? 1 : 0;
     dtype &= MDL_DTYPE_MASK;
-    int rc = bn_check("mdl_bn_apply", N, C, dtype, x);
+    const BnPtr ptrs[] = {{"x", x, true}, {"sums", sums, false}, {"save", save, false}, {"y", y, true}};
+    int rc = bn_check("mdl_bn_apply", N, C, dtype, ptrs);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     int64_t g = cdiv(N * (C / bn_width(C, dtype)), 256 * 4);
@@ -302,7 +314,8 @@ extern "C" int mdl_bn_bwd_stats_n(const void* dy, const void* x, const float* sa
     using namespace mdl;
     const bool det = (dtype & MDL_DETERMINISTIC) != 0;
     dtype &= MDL_DTYPE_MASK;
-    int rc = bn_check("mdl_bn_bwd_stats", N, C, dtype, x);
+    const BnPtr ptrs[] = {{"dy", dy, true}, {"x", x, true}, {"save", save, false}, {"sums", sums, false}};
+    int rc = bn_check("mdl_bn_bwd_stats", N, C, dtype, ptrs);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int W = bn_width(C, dtype);
@@ -316,7 +329,8 @@ static int bn_bwd_apply_launch(const char* name, bool mask, const void* dy, cons
                                void* dx, int64_t N, int C, const int64_t* n_dev, int dtype, mdlStream_t stream) {
     using namespace mdl;
     dtype &= MDL_DTYPE_MASK;
-    int rc = bn_check(name, N, C, dtype, x);
+    const BnPtr ptrs[] = {{"dy", dy, true}, {"x", x, true}, {"save", save, false}, {"sums", sums, false}, {"dx", dx, true}};
+    int rc = bn_check(name, N, C, dtype, ptrs);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     int64_t g = cdiv(N * (C / bn_width(C, dtype)), 256 * 4);
