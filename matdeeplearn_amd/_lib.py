@@ -154,6 +154,13 @@ PROTOTYPES = {
     "mdl_md_velocities": (_i32, [_vp] * 4 + [_i64, _i64, _vp, _vp, _i32, _vp]),
 }
 
+# the analysis layer (include/mdl_hip_analysis.h, csrc/observe.hip): a table of its own, registered on the same library
+_f64 = ctypes.c_double
+ANALYSIS_PROTOTYPES = {
+    "mdl_rdf_accumulate": (_i32, [_vp] * 6 + [_i64, _i64, _i64, _f64, _i32, _i32] + [_vp] * 4 + [_vp]),
+    "mdl_msd_accumulate": (_i32, [_vp] * 8 + [_i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -170,7 +177,7 @@ def lib():
                 "libmdl_hip.so not found at %s — build it with `python -m matdeeplearn_amd._build` "
                 "(hipcc --offload-arch=gfx950).  matdeeplearn_amd has no CPU/eager fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in list(PROTOTYPES.items()) + list(ANALYSIS_PROTOTYPES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
         _lib = handle

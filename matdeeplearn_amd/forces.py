@@ -31,8 +31,14 @@ NVE or Langevin, one launch per step too (ops.md_step, csrc/md.hip), with counte
 same alone and in any batch; md_npt is md at a pressure: an isotropic barostat (stochastic cell rescaling), driven by the strain
 gradient, inside the same launch (ops.md_cell_step).  neb finds the barrier between two minima: the images of nudged elastic bands are the structures of ONE
 ForceField, the band force (improved tangent, springs, climbing image) of every image is one launch (csrc/neb.hip) and FIRE then
-moves every band as one object (ops.neb_step: the band mode of mdl_fire_step); interpolate_band makes a band from two end points."""
+moves every band as one object (ops.neb_step: the band mode of mdl_fire_step); interpolate_band makes a band from two end points.
+sample is md or md_npt with the trajectory's observables recorded on the way, as an Observe asks: per sampled step one launch for
+the pair histograms of the whole batch over every periodic image (ops.rdf_accumulate) and one for the mean-squared displacements
+against a ring of time origins (ops.msd_accumulate), both csrc/observe.hip behind include/mdl_hip_analysis.h, and plain copies for
+stored frames; no host read, the run's bits unchanged.  Observations holds the accumulators and turns them into g(r), MSD and a
+diffusion coefficient."""
 import collections
+import inspect
 import math
 
 import numpy as np
@@ -646,12 +652,13 @@ def md(model, structs, dist_range, masses, dt, steps, kT=0.0, gamma=0.0, kT_init
 
 
 def _md(who, model, structs, dist_range, masses, dt, steps, kT, gamma, kT_init, velocities, seed, fixed, rebuild_every, max_disp, check_every,
-        ff_args, baro=None):
+        ff_args, baro=None, observe=None):
     """md and md_npt (`who`) behind their arguments: the checks, the ForceField, the velocities and the rebuild / evaluate / step
     loop.  baro: None (ops.md_step on the forces alone), or md_npt's (pressure, rate, max_strain) as [B] host arrays and a number
     (ops.md_cell_step on forces and strain gradient; the kernel writes ff.cell).  Returns (the ForceField, the velocities, the
     state, what the last evaluation returned, the traces: prediction and state.ekin — with baro also state.volume and
-    state.pressure — at every evaluation)."""
+    state.pressure — at every evaluation).  observe: None (md, md_npt: the launches are what they were), or sample's _Observer: it is
+    told the run once and called at every evaluation, before that step's integrator launch; it reads positions, cell and status."""
     _accepted(model, dist_range)
     if model.training:
         raise ops.MdlError("%s: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
@@ -688,9 +695,13 @@ def _md(who, model, structs, dist_range, masses, dt, steps, kT, gamma, kT_init, 
         pressure_t, rate_t = [_per_structure(v, B, dev, who, name) for name, v in (("pressure", baro[0]), ("rate", baro[1]))]
     n_steps = torch.full((B,), steps, dtype=torch.int32, device=dev)
     traces = None
+    if observe is not None:
+        observe.start(ff, mass, fixed, dt_t, steps, baro is not None)
     for it in range(steps + 1):
         if it > 0 and rebuild_every > 0 and it % rebuild_every == 0:
             ff.rebuild()
+        if observe is not None:
+            observe.sample(it, ff, state.status)
         if baro is None:
             out = ff.evaluate()
             ops.md_step(ff.positions, vel, out[1], mass, ff.node_ptr, state, dt_t, n_steps, gamma_t, kT_t, seed_t, fixed, max_disp)
@@ -741,6 +752,13 @@ def md_npt(model, structs, dist_range, masses, dt, steps, pressure, tau_p, compr
     int32 (1 finished, 2 stopped by max_disp, 3 stopped by max_strain, 0 still running), epot_trace [steps + 1, B(, out)] fp32,
     ekin_trace, volume_trace, pressure_trace [steps + 1, B] float64, node_ptr), device tensors.  No host read beyond md's.  With
     ops.deterministic() two calls return the same bits."""
+    return _md_npt(None, model, structs, dist_range, masses, dt, steps, pressure, tau_p, compressibility, kT, gamma, kT_init, velocities, seed,
+                   fixed, rebuild_every, max_disp, max_strain, check_every, radius, max_neighbors, dictionary, output_index)
+
+
+def _md_npt(observe, model, structs, dist_range, masses, dt, steps, pressure, tau_p, compressibility, kT, gamma, kT_init, velocities, seed, fixed,
+            rebuild_every, max_disp, max_strain, check_every, radius, max_neighbors, dictionary, output_index):
+    """md_npt behind its arguments (observe: as _md)"""
     who = "md_npt"
     p = _packed(structs)
     B = len(_host(p["node_ptr"], np.int64)) - 1
@@ -768,6 +786,220 @@ def md_npt(model, structs, dist_range, masses, dt, steps, pressure, tau_p, compr
                            "their barostat off)" % (who, np.nonzero(open_ & (rate > 0))[0].tolist()))
     ff, vel, state, (energy, f), (epot_trace, ekin_trace, volume_trace, pressure_trace) = _md(
         who, model, p, dist_range, masses, dt, steps, kT, gamma, kT_init, velocities, seed, fixed, rebuild_every, max_disp, check_every,
-        (radius, max_neighbors, dictionary, output_index), (press, rate, float(max_strain)))
+        (radius, max_neighbors, dictionary, output_index), (press, rate, float(max_strain)), observe)
     return NPTResult(ff.positions, vel, ff.cell, energy, f, state.ekin, state.volume, state.pressure, state.steps, state.status, epot_trace,
                      ekin_trace, volume_trace, pressure_trace, ff.node_ptr)
+
+
+# ------------------------------------------------------------------------------------------------
+# Trajectory observables: what a run of md / md_npt leaves behind besides its last frame
+# ------------------------------------------------------------------------------------------------
+class Observe:
+    """What forces.sample is to record along a run, all of it on the device (no host read, the run's bits unchanged):
+      every         sample every this many steps (>= 1) ...
+      skip          ... from this step on (>= 0): equilibration steps are not sampled.  Step `it` (0 .. steps, the positions after
+                    `it` steps) is sampled if it >= skip and (it - skip) % every == 0
+      rdf           None, or dict(r_max, nbins): the pair histogram of every structure out to r_max (every periodic image) in nbins
+                    bins, per unordered pair of types
+      msd           None, or dict(n_lags, origin_every, remove_com=True[, n_origins]): the mean-squared displacement per type at lags
+                    of 0 .. n_lags - 1 SAMPLES against a ring of time origins, a new one every origin_every samples
+                    (n_origins slots, by default ceil(n_lags / origin_every): every origin lives until its lag reaches n_lags);
+                    remove_com: the displacement of the centre of mass of the structure's free atoms is taken out first
+      frames_every  0, or store the positions (and, under NPT, the cells) of every this many steps — plain copies into [F, N, 3] /
+                    [F, B, 3, 3] device tensors, F = steps // frames_every + 1
+      types         None: one type per distinct atomic number of the batch, in sorted order; or an explicit [N] array of integers
+                    >= 0 in the order of the packed structures
+    The numbers are checked here; what needs the structures (the length of types, T (T + 1) / 2 * nbins against the kernel's
+    histogram) is checked by forces.sample before it asks a device for anything."""
+
+    def __init__(self, every=1, skip=0, rdf=None, msd=None, frames_every=0, types=None):
+        self.every, self.skip, self.frames_every = int(every), int(skip), int(frames_every)
+        if self.every < 1 or self.skip < 0 or self.frames_every < 0:
+            raise ops.MdlError("Observe: every must be >= 1, skip and frames_every >= 0 (got %r, %r, %r)" % (every, skip, frames_every))
+        self.rdf, self.msd = ops.observe_numbers("Observe", None, rdf, msd)
+        self.types = None
+        if types is not None:
+            t = np.asarray(types.detach().cpu() if torch.is_tensor(types) else types)
+            if t.ndim != 1 or t.dtype.kind not in "iu":
+                raise ops.MdlError("Observe: types must be a one-dimensional integer array (got %s %s)" % (t.shape, t.dtype))
+            if t.size and int(t.min()) < 0:
+                raise ops.MdlError("Observe: types must be >= 0 (got %d)" % int(t.min()))
+            self.types = t.astype(np.int64)
+
+
+class Observations:
+    """What forces.sample recorded: device tensors and small torch helpers.
+      hist [B, P, nbins] int64 (ordered pairs (i, j, image) per unordered type pair, P = T (T + 1) / 2), frames [B] int64 (frames
+      counted per structure), vol_sum [B] float64 (sum of |det cell| over them), flag [B] int32 (ops.RDF_* bits: why a structure
+      was not counted) — None without rdf;  msd_sum [B, T, n_lags] float64, msd_count [B, n_lags] int64 — None without msd;
+      types [N] int32, species (the atomic number of every type, or None with explicit types), type_counts [B, T] (FREE atoms per
+      type: what msd averages over), type_totals [B, T] (all atoms: what g normalises with);
+      frames_pos [F, N, 3], frames_cell [F, B, 3, 3] (NPT only) float64 and frames_step [F] int64 (the step of every stored frame,
+      -1: the loop ended before it) — None without frames_every;  lag_time [B] float64: dt * every, the time between two samples."""
+
+    def __init__(self, state, species, type_counts, type_totals, frames_pos, frames_cell, frames_step, lag_time, pbc):
+        self._state, self.species, self.type_counts, self.type_totals = state, species, type_counts, type_totals
+        self.frames_pos, self.frames_cell, self.frames_step, self.lag_time, self._pbc = frames_pos, frames_cell, frames_step, lag_time, pbc
+        for k in ("hist", "frames", "vol_sum", "flag", "msd_sum", "msd_count", "types", "r_max", "nbins", "n_lags"):
+            setattr(self, k, getattr(state, k))
+
+    def _asked(self, what, field):
+        if field is None:
+            raise ops.MdlError("Observations.%s: the run was not asked for it (forces.Observe)" % what)
+
+    def r(self):
+        """[nbins] float64: the bin centres"""
+        self._asked("r", self.hist)
+        return (torch.arange(self.nbins, dtype=torch.float64, device=self.hist.device) + 0.5) * (self.r_max / self.nbins)
+
+    def counts(self, a, b):
+        """[B, nbins] float64: ordered pairs of types (a, b) per frame and bin — for a != b both (a, b) and (b, a) — NaN for a
+        structure without a counted frame.  This is what a cluster or a slab has in the place of g."""
+        self._asked("counts", self.hist)
+        fr = self.frames.double()
+        return self.hist[:, self._state.pair_index(a, b)].double() / torch.where(fr > 0, fr, torch.full_like(fr, float("nan"))).unsqueeze(1)
+
+    def g(self, a, b):
+        """[B, nbins] float64: the radial distribution function of types (a, b) per structure, hist / (frames N_a N_b / <V> shell
+        volume) (a != b: over 2, hist holds both orders) with <V> = vol_sum / frames, the MEAN volume of the sampled frames — a
+        choice: under NPT normalising frame by frame differs at second order in the volume fluctuation.  MdlError if a structure
+        of the batch is not periodic along all three axes: it has no density (counts gives its pairs per frame)."""
+        self._asked("g", self.hist)
+        if ((self._pbc & 7) != 7).any():
+            raise ops.MdlError("Observations.g: structures %s are not periodic along all three axes: they have no density (counts(a, b) "
+                               "gives their pairs per frame)" % np.nonzero((self._pbc & 7) != 7)[0].tolist())
+        edges = torch.arange(self.nbins + 1, dtype=torch.float64, device=self.hist.device) * (self.r_max / self.nbins)
+        shell = (4.0 / 3.0) * math.pi * (edges[1:] ** 3 - edges[:-1] ** 3)
+        fr = self.frames.double()
+        density = fr * self.type_totals[:, int(a)].double() * self.type_totals[:, int(b)].double() / (self.vol_sum / fr)
+        return self.hist[:, self._state.pair_index(a, b)].double() / (density.unsqueeze(1) * shell * (1.0 if int(a) == int(b) else 2.0))
+
+    def msd(self, t):
+        """[B, n_lags] float64: the mean-squared displacement of the free atoms of type t at lags of 0 .. n_lags - 1 samples
+        (lag_time each), NaN where no sample reached the lag (msd_count == 0) or the structure has no free atom of the type"""
+        self._asked("msd", self.msd_sum)
+        n = self.msd_count.double() * self.type_counts[:, int(t)].double().unsqueeze(1)
+        return torch.where(n > 0, self.msd_sum[:, int(t)] / n, torch.full_like(n, float("nan")))
+
+    def diffusion(self, t, lag_lo, lag_hi):
+        """[B] float64: the least-squares slope of msd(t) over the lags lag_lo .. lag_hi - 1 against time (lag * lag_time), over 6"""
+        lag_lo, lag_hi = int(lag_lo), int(lag_hi)
+        self._asked("diffusion", self.msd_sum)
+        if not 0 <= lag_lo < lag_hi - 1 or lag_hi > self.n_lags:
+            raise ops.MdlError("Observations.diffusion: need 0 <= lag_lo < lag_hi - 1 and lag_hi <= n_lags = %d" % self.n_lags)
+        y = self.msd(t)[:, lag_lo:lag_hi]
+        x = torch.arange(lag_lo, lag_hi, dtype=torch.float64, device=y.device).unsqueeze(0) * self.lag_time.unsqueeze(1)
+        xc, yc = x - x.mean(1, keepdim=True), y - y.mean(1, keepdim=True)
+        return (xc * yc).sum(1) / (xc * xc).sum(1) / 6.0
+
+
+class _Observer:
+    """forces.sample's side of _md's hook.  Everything that decides WHEN something is sampled is host arithmetic, done here once:
+    the sampled steps, the ring of origins and the lag of every slot at every sample (ops.msd_schedule, uploaded as one table)."""
+
+    def __init__(self, req, p, steps):
+        who = "sample"
+        z, node_ptr = _host(p["numbers"], np.int64), _host(p["node_ptr"], np.int64)
+        N = len(z)
+        if req.types is None:
+            self.species = np.unique(z)
+            self.types = np.searchsorted(self.species, z)
+        else:
+            if req.types.shape != (N,):
+                raise ops.MdlError("%s: Observe.types must be [N] with N = %d (got %s)" % (who, N, req.types.shape))
+            self.species, self.types = None, req.types
+        self.T = int(self.types.max()) + 1 if N else 1
+        self.rdf, self.msd = ops.observe_numbers(who, self.T, req.rdf, req.msd)
+        self.req, self.node_ptr, self.pbc = req, node_ptr, _host(p["pbc"], np.int32)
+        self.sample_of = {it: s for s, it in enumerate(range(req.skip, int(steps) + 1, req.every))}
+        self.state = None
+
+    def start(self, ff, mass, fixed, dt, steps, npt):
+        dev, N, B = ff.positions.device, ff.positions.shape[0], ff.node_ptr.numel() - 1
+        self.state = ops.observe_state(self.types, self.node_ptr, self.T, self.rdf, self.msd, dev)
+        self.mass, self.fixed = mass, fixed
+        if self.msd is not None:
+            slot, lag = ops.msd_schedule(len(self.sample_of), self.msd["n_lags"], self.msd["origin_every"], self.msd["n_origins"])
+            self.slot, self.lag = slot.tolist(), lag.to(dev)
+        flat = _batch_index(ff.node_ptr, N) * self.T + self.state.types.long()
+        count = lambda w: torch.zeros(B * self.T, dtype=torch.int64, device=dev).index_add_(0, flat, w).view(B, self.T)
+        ones = torch.ones(N, dtype=torch.int64, device=dev)
+        self.type_totals, self.type_counts = count(ones), count(ones if fixed is None else (fixed == 0).long())
+        self.lag_time = dt * float(self.req.every)
+        self.frames_pos = self.frames_cell = self.frames_step = None
+        if self.req.frames_every > 0:
+            F = steps // self.req.frames_every + 1
+            self.frames_pos = torch.full((F, N, 3), float("nan"), dtype=torch.float64, device=dev)
+            self.frames_cell = torch.full((F, B, 3, 3), float("nan"), dtype=torch.float64, device=dev) if npt else None
+            self.frames_step = [-1] * F
+
+    def sample(self, it, ff, status):
+        every = self.req.frames_every
+        if every > 0 and it % every == 0:
+            self.frames_pos[it // every].copy_(ff.positions)
+            if self.frames_cell is not None:
+                self.frames_cell[it // every].copy_(ff.cell)
+            self.frames_step[it // every] = it
+        s = self.sample_of.get(it)
+        if s is None:
+            return
+        if self.rdf is not None:
+            ops.rdf_accumulate(ff.positions, ff.cell, ff.pbc, self.state, status)
+        if self.msd is not None:
+            if self.slot[s] >= 0:
+                self.state.origins[self.slot[s]].copy_(ff.positions)
+            ops.msd_accumulate(ff.positions, self.lag[s], self.mass, self.state, self.fixed, status, self.msd["remove_com"])
+
+    def result(self):
+        steps = None if self.frames_step is None else torch.tensor(self.frames_step, dtype=torch.int64, device=self.frames_pos.device)
+        return Observations(self.state, self.species, self.type_counts, self.type_totals, self.frames_pos, self.frames_cell, steps,
+                            self.lag_time, self.pbc)
+
+
+def sample(model, structs, dist_range, masses, dt, steps, observe, npt=None, **md_kwargs):
+    """forces.md or forces.md_npt with the trajectory's observables recorded on the way: the radial distribution function, the
+    mean-squared displacement and stored frames, as `observe` (a forces.Observe) asks.  The run is the one md / md_npt make from the
+    same arguments, to the bit: sampling reads positions, cells and status words between two steps and writes nothing the
+    integrator or the force field reads.  Per SAMPLED step the loop makes one pair-histogram launch (ops.rdf_accumulate) and one
+    displacement launch (ops.msd_accumulate) before that step's integrator launch, a plain copy where a time origin or a frame is
+    stored, and nothing otherwise; no host read is added.
+
+    model, structs, dist_range, masses, dt, steps   as md
+    observe       forces.Observe(...)
+    npt           None: md's loop;  dict(pressure, tau_p, compressibility[, max_strain]): md_npt's, with its checks
+    md_kwargs     md's keyword arguments (kT, gamma, kT_init, velocities, seed, fixed, rebuild_every, max_disp, check_every, radius,
+                  max_neighbors, dictionary, output_index)
+
+    A structure that the integrator's guard has stopped (status != 0) stops contributing from the next sample on; the last
+    evaluation (step == steps) is sampled if the schedule reaches it.  Positions are unwrapped throughout, which is what the
+    displacement needs; the histogram reduces every pair to its nearest image itself.  Under NPT the barostat scales the
+    positions with the cell, and the displacement is taken on the scaled coordinates AS THEY ARE: it contains the affine motion
+    of the cell (small against diffusion at a stable volume; divide the frames by the cell to take it out).  g is normalised by
+    the mean volume of the sampled frames (Observations.g).
+    Returns (MDResult or NPTResult, Observations).  Counts are integer sums and the displacement sums have no atomics: two calls
+    return the same bits, and a structure's observables do not depend on the batch it is in as far as its trajectory does not."""
+    who = "sample"
+    if not isinstance(observe, Observe):
+        raise ops.MdlError("%s: observe must be a forces.Observe (got %s)" % (who, type(observe).__name__))
+    kw = {k: v.default for k, v in inspect.signature(md).parameters.items() if v.default is not inspect.Parameter.empty}
+    unknown = sorted(set(md_kwargs) - set(kw))
+    if unknown:
+        raise ops.MdlError("%s: unknown keyword arguments %s (md's are %s)" % (who, unknown, sorted(kw)))
+    kw.update(md_kwargs)
+    if npt is not None:
+        need, may = {"pressure", "tau_p", "compressibility"}, {"max_strain"}
+        if not isinstance(npt, dict) or not need <= set(npt) <= need | may:
+            raise ops.MdlError("%s: npt must be None or dict(pressure, tau_p, compressibility[, max_strain])" % who)
+    p = _packed(structs)
+    obs = _Observer(observe, p, steps)
+    ff_args = (kw["radius"], kw["max_neighbors"], kw["dictionary"], kw["output_index"])
+    if npt is None:
+        ff, vel, state, (energy, f), (epot_trace, ekin_trace) = _md(
+            "md", model, p, dist_range, masses, dt, steps, kw["kT"], kw["gamma"], kw["kT_init"], kw["velocities"], kw["seed"], kw["fixed"],
+            kw["rebuild_every"], kw["max_disp"], kw["check_every"], ff_args, None, obs)
+        res = MDResult(ff.positions, vel, energy, f, state.ekin, state.steps, state.status, epot_trace, ekin_trace, ff.node_ptr)
+    else:
+        res = _md_npt(obs, model, p, dist_range, masses, dt, steps, npt["pressure"], npt["tau_p"], npt["compressibility"], kw["kT"],
+                      kw["gamma"], kw["kT_init"], kw["velocities"], kw["seed"], kw["fixed"], kw["rebuild_every"], kw["max_disp"],
+                      npt.get("max_strain", 0.03), kw["check_every"], *ff_args)
+    return res, obs.result()

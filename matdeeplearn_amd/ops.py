@@ -3196,3 +3196,199 @@ def md_velocities(mass, node_ptr, kT, seed=0, fixed=None, zero_momentum=True):
     check(lib().mdl_md_velocities(ptr(vel), ptr(mass), ptr(fixed), ptr(node_ptr.contiguous()), N, B, ptr(kT), ptr(seed),
                                   1 if zero_momentum else 0, stream()), "mdl_md_velocities")
     return vel
+
+
+# ------------------------------------------------------------------------------------------------
+# Trajectory observables: pair histograms and mean-squared displacements of a batch, one launch per sampled frame each
+# (csrc/observe.hip, include/mdl_hip_analysis.h)
+# ------------------------------------------------------------------------------------------------
+# the limits of include/mdl_hip_analysis.h, restated here so that a request beyond them is refused before the library is loaded
+RDF_MAX_COUNTERS, RDF_MAX_IMAGES, MSD_MAX_TYPES = 8192, 16, 64
+RDF_NO_VOLUME, RDF_TOO_MANY_IMAGES, RDF_BAD_TYPE, RDF_TOO_LARGE = 1, 2, 4, 8
+
+
+def observe_numbers(who, n_types=None, rdf=None, msd=None):
+    """The ranges of what an observation is asked with — plain numbers, checked before a device or the library is asked for
+    anything.  rdf: None or dict(r_max, nbins); msd: None or dict(n_lags, origin_every[, n_origins, remove_com]).  Returns (rdf, msd)
+    as dicts with every key present (n_origins defaults to ceil(n_lags / origin_every): an origin lives until its lag is n_lags)."""
+    if n_types is not None and int(n_types) < 1:
+        raise MdlError("%s: the number of types must be >= 1 (got %r)" % (who, n_types))
+    if rdf is not None:
+        unknown = set(rdf) - {"r_max", "nbins"}
+        if unknown or "r_max" not in rdf or "nbins" not in rdf:
+            raise MdlError("%s: rdf must be dict(r_max, nbins) (got keys %s)" % (who, sorted(rdf)))
+        r_max, nbins = float(rdf["r_max"]), int(rdf["nbins"])
+        if not (r_max > 0.0 and r_max < float("inf")):
+            raise MdlError("%s: rdf: r_max must be > 0 and finite (got %r)" % (who, rdf["r_max"]))
+        if nbins < 1:
+            raise MdlError("%s: rdf: nbins must be >= 1 (got %r)" % (who, rdf["nbins"]))
+        if n_types is not None and int(n_types) * (int(n_types) + 1) // 2 * nbins > RDF_MAX_COUNTERS:
+            raise MdlError("%s: rdf: T (T + 1) / 2 * nbins = %d counters with T = %d types exceed the %d of the kernel's LDS histogram"
+                           % (who, int(n_types) * (int(n_types) + 1) // 2 * nbins, int(n_types), RDF_MAX_COUNTERS))
+        rdf = dict(r_max=r_max, nbins=nbins)
+    if msd is not None:
+        unknown = set(msd) - {"n_lags", "origin_every", "n_origins", "remove_com"}
+        if unknown or "n_lags" not in msd:
+            raise MdlError("%s: msd must be dict(n_lags, origin_every[, n_origins, remove_com]) (got keys %s)" % (who, sorted(msd)))
+        n_lags, origin_every = int(msd["n_lags"]), int(msd.get("origin_every", 1))
+        if n_lags < 1:
+            raise MdlError("%s: msd: n_lags must be >= 1 (got %r)" % (who, msd["n_lags"]))
+        if origin_every < 1:
+            raise MdlError("%s: msd: origin_every must be >= 1 (got %r)" % (who, msd["origin_every"]))
+        n_origins = msd.get("n_origins")
+        n_origins = -(-n_lags // origin_every) if n_origins is None else int(n_origins)
+        if not 1 <= n_origins <= 65535:
+            raise MdlError("%s: msd: n_origins must be in 1 .. 65535 (got %r)" % (who, n_origins))
+        if n_types is not None and int(n_types) > MSD_MAX_TYPES:
+            raise MdlError("%s: msd: at most %d types (got %d)" % (who, MSD_MAX_TYPES, int(n_types)))
+        msd = dict(n_lags=n_lags, origin_every=origin_every, n_origins=n_origins, remove_com=bool(msd.get("remove_com", True)))
+    return rdf, msd
+
+
+def msd_schedule(n_samples, n_lags, origin_every, n_origins):
+    """The ring of time origins as host arithmetic, for samples s = 0 .. n_samples - 1: (slot [n_samples] — the slot that takes the
+    positions of sample s as a new origin BEFORE the sample is accumulated, every origin_every samples into (s // origin_every) %
+    n_origins, else -1 —, lag [n_samples, n_origins] int32 — how many samples ago the origin of every slot was stored, -1 where the
+    slot is empty or its lag has reached n_lags).  Live slots of a sample have distinct lags; lag 0 is the origin just stored."""
+    n_samples, n_lags, origin_every, n_origins = int(n_samples), int(n_lags), int(origin_every), int(n_origins)
+    slot = torch.full((n_samples,), -1, dtype=torch.int64)
+    lag = torch.full((n_samples, n_origins), -1, dtype=torch.int32)
+    stored = [-1] * n_origins
+    for s in range(n_samples):
+        if s % origin_every == 0:
+            slot[s] = (s // origin_every) % n_origins
+            stored[int(slot[s])] = s
+        for k, s0 in enumerate(stored):
+            if s0 >= 0 and s - s0 < n_lags:
+                lag[s, k] = s - s0
+    return slot, lag
+
+
+class ObserveState:
+    """The accumulators of rdf_accumulate and msd_accumulate, device tensors allocated once (ops.observe_state):
+      types [N] int32, node_ptr [B + 1] int64, n_types T, max_atoms (the largest structure: it sizes the histogram's grid)
+      rdf: r_max, nbins; hist [B, T (T + 1) / 2, nbins] int64 — the unordered pair (a <= b) at pair_index(a, b) —, frames [B] int64,
+           vol_sum [B] float64, flag [B] int32 (bits RDF_NO_VOLUME, RDF_TOO_MANY_IMAGES, RDF_BAD_TYPE, RDF_TOO_LARGE)
+      msd: n_lags, origins [K, N, 3] float64 (the ring; the caller stores an origin with origins[k].copy_(pos)), msd_sum [B, T, n_lags]
+           float64, msd_count [B, n_lags] int64
+    What was not asked for is None."""
+
+    __slots__ = ("types", "node_ptr", "n_types", "max_atoms", "r_max", "nbins", "hist", "frames", "vol_sum", "flag", "n_lags", "origins",
+                 "msd_sum", "msd_count")
+
+    def pair_index(self, a, b):
+        a, b = (int(a), int(b)) if int(a) <= int(b) else (int(b), int(a))
+        if not 0 <= a <= b < self.n_types:
+            raise MdlError("pair_index: types must be in 0 .. %d (got %d, %d)" % (self.n_types - 1, a, b))
+        return a * self.n_types - a * (a - 1) // 2 + (b - a)
+
+
+def _host_ints(who, name, v):
+    t = v.detach().cpu() if torch.is_tensor(v) else torch.as_tensor(v)
+    if t.dtype in (torch.float16, torch.float32, torch.float64, torch.bfloat16, torch.bool) or t.dim() != 1:
+        raise MdlError("%s: %s must be a one-dimensional integer array (got %s %s)" % (who, name, tuple(t.shape), t.dtype))
+    return t.to(torch.int64)
+
+
+def observe_state(types, node_ptr, n_types=None, rdf=None, msd=None, device=None):
+    """A fresh ObserveState.  types [N] integers in 0 .. n_types - 1 (n_types None: the largest type + 1) and node_ptr [B + 1], arrays
+    or tensors: their values are looked at here, once — a device tensor is read back — so that no launch sees a type it cannot
+    index or a structure larger than its grid.  rdf: None or dict(r_max, nbins) with T (T + 1) / 2 * nbins <= RDF_MAX_COUNTERS; msd:
+    None or dict(n_lags[, origin_every, n_origins]) (the state keeps n_lags and a ring of n_origins slots; the schedule is the
+    caller's: ops.msd_schedule).  Every argument error raises before a device or the library is asked for anything."""
+    who = "observe_state"
+    observe_numbers(who, n_types, rdf, msd)
+    th, ph = _host_ints(who, "types", types), _host_ints(who, "node_ptr", node_ptr)
+    N, B = th.numel(), ph.numel() - 1
+    if B < 0 or (B >= 0 and (int(ph[0]) != 0 or int(ph[-1]) != N or bool((ph[1:] < ph[:-1]).any()))):
+        raise MdlError("%s: node_ptr must start at 0, be non-decreasing and end at N = %d" % (who, N))
+    T = int(n_types) if n_types is not None else (int(th.max()) + 1 if N else 1)
+    if N and (int(th.min()) < 0 or int(th.max()) >= T):
+        raise MdlError("%s: types must be in 0 .. %d (got %d .. %d)" % (who, T - 1, int(th.min()), int(th.max())))
+    rdf, msd = observe_numbers(who, T, rdf, msd)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    st = ObserveState()
+    for k in ObserveState.__slots__:
+        setattr(st, k, None)
+    st.types = (types.detach().to(dev, torch.int32) if torch.is_tensor(types) else th.to(torch.int32).to(dev)).contiguous()
+    st.node_ptr = (node_ptr.detach().to(dev, torch.int64) if torch.is_tensor(node_ptr) else ph.to(dev)).contiguous()
+    st.n_types, st.max_atoms = T, int((ph[1:] - ph[:-1]).max()) if B > 0 else 0
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+    if rdf is not None:
+        st.r_max, st.nbins = rdf["r_max"], rdf["nbins"]
+        st.hist, st.frames = z((B, T * (T + 1) // 2, st.nbins), torch.int64), z((B,), torch.int64)
+        st.vol_sum, st.flag = z((B,), torch.float64), z((B,), torch.int32)
+    if msd is not None:
+        st.n_lags = msd["n_lags"]
+        st.origins = z((msd["n_origins"], N, 3), torch.float64)
+        st.msd_sum, st.msd_count = z((B, T, st.n_lags), torch.float64), z((B, st.n_lags), torch.int64)
+    return st
+
+
+def _observe_common(who, pos, state, status, asked):
+    if not isinstance(state, ObserveState) or getattr(state, asked) is None:
+        raise MdlError("%s: state must be an ops.ObserveState made for it (ops.observe_state)" % who)
+    if not torch.is_tensor(pos) or pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 3 or not pos.is_contiguous():
+        raise MdlError("%s: pos must be a contiguous [N, 3] float64 tensor (got %s %s)"
+                       % (who, tuple(getattr(pos, "shape", ())), getattr(pos, "dtype", type(pos))))
+    N, B = state.types.numel(), state.node_ptr.numel() - 1
+    if pos.shape[0] != N:
+        raise MdlError("%s: pos must be [N, 3] with N = %d, the atoms of the state (got %s)" % (who, N, tuple(pos.shape)))
+    if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int32 or tuple(status.shape) != (B,)
+                               or not status.is_contiguous()):
+        raise MdlError("%s: status must be a contiguous [B] int32 tensor with B = %d, or None" % (who, B))
+    return N, B
+
+
+def rdf_accumulate(pos, cell, pbc, state, status=None):
+    """One frame into the pair histograms of a batch: ONE launch, no host read (include/mdl_hip_analysis.h, mdl_rdf_accumulate).
+      pos [N, 3] float64, unwrapped; cell [B, 3, 3] float64, rows are lattice vectors; pbc [B] int32, one bit per periodic axis;
+      state an ObserveState made with rdf=dict(r_max, nbins) (its types and node_ptr are used); status [B] int32 or None: structures
+      with a non-zero status are skipped (ops.md_step sets it where its guard stopped a structure).
+    For every structure every ordered pair (i, j, image) with 0 < r < r_max — every periodic image, whatever the skew of the cell
+    and however far the unwrapped atoms have drifted — is counted in state.hist[b, pair, (int)(r nbins / r_max)]; state.frames[b] += 1
+    and state.vol_sum[b] += |det cell|.  A structure whose periodic axes span no volume, or that needs more than RDF_MAX_IMAGES
+    images along an axis, is not counted and gets a bit in state.flag.  Integer counts: the same bits on every run and in any
+    batch.  Returns state."""
+    who = "rdf_accumulate"
+    N, B = _observe_common(who, pos, state, status, "hist")
+    if not torch.is_tensor(cell) or cell.dtype != torch.float64 or tuple(cell.shape) != (B, 3, 3) or not cell.is_contiguous():
+        raise MdlError("%s: cell must be a contiguous [B, 3, 3] float64 tensor with B = %d" % (who, B))
+    if not torch.is_tensor(pbc) or pbc.dtype != torch.int32 or tuple(pbc.shape) != (B,) or not pbc.is_contiguous():
+        raise MdlError("%s: pbc must be a contiguous [B] int32 tensor (one bit per axis) with B = %d" % (who, B))
+    require_hip(pos, cell, pbc, status, state.hist)
+    if any(t.device != pos.device for t in (cell, pbc, state.hist) + (() if status is None else (status,))):
+        raise MdlError("%s: pos, cell, pbc, status and the state must be on one device" % who)
+    check(lib().mdl_rdf_accumulate(ptr(pos), ptr(state.types), ptr(state.node_ptr), ptr(cell), ptr(pbc), ptr(status), N, B, state.max_atoms,
+                                   float(state.r_max), int(state.nbins), int(state.n_types), ptr(state.hist), ptr(state.frames),
+                                   ptr(state.vol_sum), ptr(state.flag), stream()), "mdl_rdf_accumulate")
+    return state
+
+
+def msd_accumulate(pos, lag, mass, state, fixed=None, status=None, remove_com=True):
+    """One frame into the mean-squared displacements of a batch against the ring of origins state.origins: ONE launch, no host read
+    (include/mdl_hip_analysis.h, mdl_msd_accumulate).
+      pos [N, 3] float64; lag [K] int32 ON THE DEVICE, one per slot of the ring: how many samples ago state.origins[k] was stored,
+      negative: skip the slot (a row of ops.msd_schedule's table; live slots must have distinct lags); mass [N] float64; state an
+      ObserveState made with msd=...; fixed [N] uint8 / bool or None (fixed atoms are left out); status as rdf_accumulate.
+    state.msd_sum[b, t, lag[k]] += the sum over the free atoms of type t of |x - x0 - D|^2, D the displacement of the free atoms'
+    centre of mass since that origin (remove_com) or 0; state.msd_count[b, lag[k]] += 1.  No atomics: the same bits on every run,
+    alone and in any batch.  Returns state."""
+    who = "msd_accumulate"
+    N, B = _observe_common(who, pos, state, status, "msd_sum")
+    K = state.origins.shape[0]
+    if not torch.is_tensor(lag) or lag.dtype != torch.int32 or tuple(lag.shape) != (K,) or not lag.is_contiguous():
+        raise MdlError("%s: lag must be a contiguous [K] int32 tensor with K = %d, the slots of state.origins" % (who, K))
+    if not torch.is_tensor(mass) or mass.dtype != torch.float64 or tuple(mass.shape) != (N,) or not mass.is_contiguous():
+        raise MdlError("%s: mass must be a contiguous [N] float64 tensor with N = %d" % (who, N))
+    if fixed is not None:
+        if not torch.is_tensor(fixed) or fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
+            raise MdlError("%s: fixed must be [N] uint8 or bool with N = %d, or None" % (who, N))
+        fixed = fixed.contiguous().view(torch.uint8)
+    require_hip(pos, lag, mass, fixed, status, state.msd_sum)
+    if any(t.device != pos.device for t in (lag, mass, state.msd_sum) + tuple(t for t in (fixed, status) if t is not None)):
+        raise MdlError("%s: pos, lag, mass, fixed, status and the state must be on one device" % who)
+    check(lib().mdl_msd_accumulate(ptr(pos), ptr(state.origins), ptr(lag), ptr(mass), ptr(state.types), ptr(fixed), ptr(state.node_ptr),
+                                   ptr(status), N, B, K, int(state.n_types), int(state.n_lags), 1 if remove_com else 0, ptr(state.msd_sum),
+                                   ptr(state.msd_count), stream()), "mdl_msd_accumulate")
+    return state
