@@ -20,7 +20,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 FILE_FLAGS = {"cgconv_ep.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "cfconv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
               "graph_build.hip": ["-ffp-contract=off"],
               # the same pair distances from the shared csrc/graph_geom.inc, the same bits
-              "edge_geom.hip": ["-ffp-contract=off"]}
+              "edge_geom.hip": ["-ffp-contract=off"],
+              # the on-step velocity restates one statement of csrc/md.hip: the integrator's bits, so nothing may be contracted
+              "vacf.hip": ["-ffp-contract=off"]}
 # translation units that #include another .hip file
 FILE_DEPS = {}
 
@@ -38,7 +40,7 @@ def sources():
 
 def _deps_mtime():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("mdl_hip.h", "mdl_hip_analysis.h")]
+    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("mdl_hip.h", "mdl_hip_analysis.h", "mdl_hip_dynamics.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -161,6 +161,12 @@ ANALYSIS_PROTOTYPES = {
     "mdl_msd_accumulate": (_i32, [_vp] * 8 + [_i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
 }
 
+# the time-correlation layer (include/mdl_hip_dynamics.h, csrc/vacf.hip): the third table
+DYNAMICS_PROTOTYPES = {
+    "mdl_md_onstep_velocity": (_i32, [_vp] * 8 + [_i64, _i64, _vp, _vp]),
+    "mdl_vacf_accumulate": (_i32, [_vp] * 8 + [_i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -177,7 +183,7 @@ def lib():
                 "libmdl_hip.so not found at %s — build it with `python -m matdeeplearn_amd._build` "
                 "(hipcc --offload-arch=gfx950).  matdeeplearn_amd has no CPU/eager fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(ANALYSIS_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(ANALYSIS_PROTOTYPES.items()) + list(DYNAMICS_PROTOTYPES.items()):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
         _lib = handle

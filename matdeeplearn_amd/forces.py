@@ -36,7 +36,10 @@ sample is md or md_npt with the trajectory's observables recorded on the way, as
 the pair histograms of the whole batch over every periodic image (ops.rdf_accumulate) and one for the mean-squared displacements
 against a ring of time origins (ops.msd_accumulate), both csrc/observe.hip behind include/mdl_hip_analysis.h, and plain copies for
 stored frames; no host read, the run's bits unchanged.  Observations holds the accumulators and turns them into g(r), MSD and a
-diffusion coefficient."""
+diffusion coefficient.  A Correlate is an Observe that also asks for the velocity autocorrelation: the on-step velocity is formed
+from what lies on the device in front of the integrator launch (ops.md_onstep_velocity) and correlated against a ring of origins
+(ops.vacf_accumulate), both csrc/vacf.hip behind include/mdl_hip_dynamics.h; Observations turns the sums into the VACF, the
+vibrational density of states and a Green-Kubo diffusion coefficient."""
 import collections
 import inspect
 import math
@@ -658,7 +661,10 @@ def _md(who, model, structs, dist_range, masses, dt, steps, kT, gamma, kT_init, 
     (ops.md_cell_step on forces and strain gradient; the kernel writes ff.cell).  Returns (the ForceField, the velocities, the
     state, what the last evaluation returned, the traces: prediction and state.ekin — with baro also state.volume and
     state.pressure — at every evaluation).  observe: None (md, md_npt: the launches are what they were), or sample's _Observer: it is
-    told the run once and called at every evaluation, before that step's integrator launch; it reads positions, cell and status."""
+    told the run once and called at every evaluation, before that step's integrator launch; it reads positions, cell and status.
+    An observer that asks for velocities (observe.velocities: a Correlate with vacf or stored frames) is called a second time between
+    the evaluation and the integrator launch, with vel, the force just evaluated, the state and dt: from these it forms the on-step
+    velocity itself (ops.md_onstep_velocity) and writes nothing the integrator or the force field reads."""
     _accepted(model, dist_range)
     if model.training:
         raise ops.MdlError("%s: the model must be in eval() mode — training-mode BatchNorm couples the structures of a batch "
@@ -702,11 +708,12 @@ def _md(who, model, structs, dist_range, masses, dt, steps, kT, gamma, kT_init, 
             ff.rebuild()
         if observe is not None:
             observe.sample(it, ff, state.status)
+        out = ff.evaluate() if baro is None else ff.evaluate(stress=True, volume_normalised=False)
+        if observe is not None and observe.velocities:
+            observe.sample_velocities(it, vel, out[1], state, dt_t)
         if baro is None:
-            out = ff.evaluate()
             ops.md_step(ff.positions, vel, out[1], mass, ff.node_ptr, state, dt_t, n_steps, gamma_t, kT_t, seed_t, fixed, max_disp)
         else:
-            out = ff.evaluate(stress=True, volume_normalised=False)
             ops.md_cell_step(ff.positions, vel, ff.cell, out[1], out[2], mass, ff.node_ptr, state, dt_t, n_steps, pressure_t, rate_t, gamma_t,
                              kT_t, seed_t, fixed, max_disp, baro[2])
         if traces is None:
@@ -827,6 +834,19 @@ class Observe:
             self.types = t.astype(np.int64)
 
 
+class Correlate(Observe):
+    """An Observe that also asks what the trajectory says about time: every, skip, rdf, msd, frames_every, types as Observe, and
+      vacf          None, or dict(n_lags, origin_every, remove_com=True[, n_origins]), ranges and defaults as msd: the velocity
+                    autocorrelation per type at lags of 0 .. n_lags - 1 samples against a ring of time origins; remove_com: the
+                    velocity of the centre of mass of the structure's free atoms is taken out of both factors first
+    The velocity is the ON-STEP velocity, the one at the evaluated positions (ops.md_onstep_velocity restates the integrator's closing
+    half kick on the force just evaluated); with frames_every > 0 it is stored next to the positions (Observations.frames_vel)."""
+
+    def __init__(self, every=1, skip=0, rdf=None, msd=None, frames_every=0, types=None, vacf=None):
+        Observe.__init__(self, every, skip, rdf, msd, frames_every, types)
+        self.vacf = ops.vacf_numbers("Correlate", None, vacf)
+
+
 class Observations:
     """What forces.sample recorded: device tensors and small torch helpers.
       hist [B, P, nbins] int64 (ordered pairs (i, j, image) per unordered type pair, P = T (T + 1) / 2), frames [B] int64 (frames
@@ -835,13 +855,20 @@ class Observations:
       types [N] int32, species (the atomic number of every type, or None with explicit types), type_counts [B, T] (FREE atoms per
       type: what msd averages over), type_totals [B, T] (all atoms: what g normalises with);
       frames_pos [F, N, 3], frames_cell [F, B, 3, 3] (NPT only) float64 and frames_step [F] int64 (the step of every stored frame,
-      -1: the loop ended before it) — None without frames_every;  lag_time [B] float64: dt * every, the time between two samples."""
+      -1: the loop ended before it) — None without frames_every;  lag_time [B] float64: dt * every, the time between two samples.
+      With a forces.Correlate: vacf_sum [B, 2, T, n_lags] float64 (plane 0: the sum of u . u0 over the free atoms of a type, plane 1:
+      of m u . u0) and vacf_count [B, n_lags] int64 — None without vacf;  frames_vel [F, N, 3] float64, the ON-STEP velocities of the
+      stored frames (the rows of a structure that the integrator has stopped are those last formed for it) — None without
+      frames_every or with a plain Observe."""
 
-    def __init__(self, state, species, type_counts, type_totals, frames_pos, frames_cell, frames_step, lag_time, pbc):
+    def __init__(self, state, species, type_counts, type_totals, frames_pos, frames_cell, frames_step, lag_time, pbc, vacf_state=None,
+                 frames_vel=None):
         self._state, self.species, self.type_counts, self.type_totals = state, species, type_counts, type_totals
         self.frames_pos, self.frames_cell, self.frames_step, self.lag_time, self._pbc = frames_pos, frames_cell, frames_step, lag_time, pbc
         for k in ("hist", "frames", "vol_sum", "flag", "msd_sum", "msd_count", "types", "r_max", "nbins", "n_lags"):
             setattr(self, k, getattr(state, k))
+        self.vacf_sum, self.vacf_count = (None, None) if vacf_state is None else (vacf_state.vacf_sum, vacf_state.vacf_count)
+        self.frames_vel = frames_vel
 
     def _asked(self, what, field):
         if field is None:
@@ -892,6 +919,48 @@ class Observations:
         xc, yc = x - x.mean(1, keepdim=True), y - y.mean(1, keepdim=True)
         return (xc * yc).sum(1) / (xc * xc).sum(1) / 6.0
 
+    def vacf(self, t, mass_weighted=False):
+        """[B, n_lags] float64: the velocity autocorrelation <u(0) . u(n)> of the free atoms of type t (mass_weighted: <m u(0) . u(n)>)
+        at lags of 0 .. n_lags - 1 samples (lag_time each): the sum over vacf_count · the free atoms of the type.  NaN where no
+        sample reached the lag or the structure has no free atom of the type"""
+        self._asked("vacf", self.vacf_sum)
+        n = self.vacf_count.double() * self.type_counts[:, int(t)].double().unsqueeze(1)
+        return torch.where(n > 0, self.vacf_sum[:, 1 if mass_weighted else 0, int(t)] / n, torch.full_like(n, float("nan")))
+
+    def vdos(self, t, window=True):
+        """(freq [B, n_lags], dos [B, n_lags]) float64: the vibrational density of states of the free atoms of type t, the cosine
+        transform of their mass-weighted velocity autocorrelation.  With M = n_lags - 1, dt = lag_time, N_t the free atoms of the
+        type, c_n = vacf(t, mass_weighted=True)[n] / [0] and w_n = cos^2(pi n / (2 M)) (a Hann window that ends at the last lag;
+        window=False: w_n = 1):
+            dos_k  = 4 (3 N_t) dt  sum''_n  w_n c_n cos(pi n k / M)          freq_k = k / (2 M dt),   k = 0 .. M
+        a DCT-I, sum'' giving half weight to n = 0 and n = M.  By its inverse at n = 0, sum''_k dos_k / (2 M dt) = 3 N_t exactly: the
+        density integrates (trapezoid rule over freq) to the degrees of freedom of the type.  A structure with a lag that no sample
+        reached, or without a free atom of the type, gets a NaN row.  Needs n_lags >= 2."""
+        self._asked("vdos", self.vacf_sum)
+        n_lags = self.vacf_sum.shape[-1]
+        if n_lags < 2:
+            raise ops.MdlError("Observations.vdos: needs n_lags >= 2 (got %d)" % n_lags)
+        M = n_lags - 1
+        c = self.vacf(t, mass_weighted=True)
+        c = c / c[:, :1]
+        n = torch.arange(n_lags, dtype=torch.float64, device=c.device)
+        w = torch.cos(n * (math.pi / (2.0 * M))) ** 2 if window else torch.ones_like(n)
+        w[0], w[M] = 0.5 * w[0], 0.5 * w[M]
+        basis = torch.cos(torch.outer(n, n) * (math.pi / M))                        # [n, k]
+        dt = self.lag_time.unsqueeze(1)
+        dos = 4.0 * (3.0 * self.type_counts[:, int(t)].double().unsqueeze(1)) * dt * ((c * w) @ basis)
+        return n.unsqueeze(0) / (2.0 * M * dt), dos
+
+    def diffusion_gk(self, t, lag_hi):
+        """[B] float64: the Green-Kubo diffusion coefficient of type t, a third of the trapezoid integral of vacf(t) over the lags
+        0 .. lag_hi - 1 (lag * lag_time)"""
+        lag_hi = int(lag_hi)
+        self._asked("diffusion_gk", self.vacf_sum)
+        if not 1 <= lag_hi <= self.vacf_sum.shape[-1]:
+            raise ops.MdlError("Observations.diffusion_gk: need 1 <= lag_hi <= n_lags = %d" % self.vacf_sum.shape[-1])
+        y = self.vacf(t)[:, :lag_hi]
+        return (y.sum(1) - 0.5 * (y[:, 0] + y[:, -1])) * self.lag_time / 3.0
+
 
 class _Observer:
     """forces.sample's side of _md's hook.  Everything that decides WHEN something is sampled is host arithmetic, done here once:
@@ -910,6 +979,9 @@ class _Observer:
             self.species, self.types = None, req.types
         self.T = int(self.types.max()) + 1 if N else 1
         self.rdf, self.msd = ops.observe_numbers(who, self.T, req.rdf, req.msd)
+        self.vacf = ops.vacf_numbers(who, self.T, req.vacf) if isinstance(req, Correlate) else None
+        # what _md's second hook is for: only a Correlate can ask, so a plain Observe keeps the launches it had
+        self.velocities = isinstance(req, Correlate) and (self.vacf is not None or req.frames_every > 0)
         self.req, self.node_ptr, self.pbc = req, node_ptr, _host(p["pbc"], np.int32)
         self.sample_of = {it: s for s, it in enumerate(range(req.skip, int(steps) + 1, req.every))}
         self.state = None
@@ -932,6 +1004,32 @@ class _Observer:
             self.frames_pos = torch.full((F, N, 3), float("nan"), dtype=torch.float64, device=dev)
             self.frames_cell = torch.full((F, B, 3, 3), float("nan"), dtype=torch.float64, device=dev) if npt else None
             self.frames_step = [-1] * F
+        self.vstate = self.frames_vel = None
+        if self.velocities:
+            self.ff_node_ptr = ff.node_ptr.contiguous()
+            self.onstep = torch.zeros((N, 3), dtype=torch.float64, device=dev)
+            if self.vacf is not None:
+                self.vstate = ops.vacf_state(self.types, self.node_ptr, self.T, self.vacf, dev)
+                slot, lag = ops.msd_schedule(len(self.sample_of), self.vacf["n_lags"], self.vacf["origin_every"], self.vacf["n_origins"])
+                self.vslot, self.vlag = slot.tolist(), lag.to(dev)
+            if self.req.frames_every > 0:
+                self.frames_vel = torch.full((F, N, 3), float("nan"), dtype=torch.float64, device=dev)
+
+    def sample_velocities(self, it, vel, force, state, dt):
+        """_md's second hook, between the evaluation of step `it` and its integrator launch: the on-step velocity, formed ONCE where
+        a frame is stored or the step is sampled (one launch), a plain copy per frame and per new origin, one correlation launch"""
+        every = self.req.frames_every
+        frame = every > 0 and it % every == 0
+        s = self.sample_of.get(it) if self.vstate is not None else None
+        if not frame and s is None:
+            return
+        ops.md_onstep_velocity(vel, force.contiguous(), self.mass, self.ff_node_ptr, state, dt, self.fixed, self.onstep)
+        if frame:
+            self.frames_vel[it // every].copy_(self.onstep)
+        if s is not None:
+            if self.vslot[s] >= 0:
+                self.vstate.origins[self.vslot[s]].copy_(self.onstep)
+            ops.vacf_accumulate(self.onstep, self.vlag[s], self.mass, self.vstate, self.fixed, state.status, self.vacf["remove_com"])
 
     def sample(self, it, ff, status):
         every = self.req.frames_every
@@ -953,7 +1051,7 @@ class _Observer:
     def result(self):
         steps = None if self.frames_step is None else torch.tensor(self.frames_step, dtype=torch.int64, device=self.frames_pos.device)
         return Observations(self.state, self.species, self.type_counts, self.type_totals, self.frames_pos, self.frames_cell, steps,
-                            self.lag_time, self.pbc)
+                            self.lag_time, self.pbc, self.vstate, self.frames_vel)
 
 
 def sample(model, structs, dist_range, masses, dt, steps, observe, npt=None, **md_kwargs):
@@ -976,6 +1074,14 @@ def sample(model, structs, dist_range, masses, dt, steps, observe, npt=None, **m
     positions with the cell, and the displacement is taken on the scaled coordinates AS THEY ARE: it contains the affine motion
     of the cell (small against diffusion at a stable volume; divide the frames by the cell to take it out).  g is normalised by
     the mean volume of the sampled frames (Observations.g).
+    With a forces.Correlate (an Observe with vacf=...) the loop also records the velocity autocorrelation per type, and stores the
+    velocities of the frames: on a sampled step, between the evaluation and the integrator launch, one launch forms the on-step
+    velocity from vel, the force just evaluated, the masses, dt and the integrator's step words (ops.md_onstep_velocity: the closing
+    half kick that the integrator itself applies only in its next call), a plain copy stores it where the schedule starts a new
+    origin, and one launch correlates it with the ring (ops.vacf_accumulate); on a step that only stores a frame, the first launch
+    and a copy.  Under NPT the velocity is the on-step velocity BEFORE the barostat's 1 / s scaling of that step.  Observations.vacf,
+    .vdos and .diffusion_gk turn the sums into the correlation function, the vibrational density of states and a Green-Kubo
+    diffusion coefficient.  With a plain Observe the launches are what they were.
     Returns (MDResult or NPTResult, Observations).  Counts are integer sums and the displacement sums have no atomics: two calls
     return the same bits, and a structure's observables do not depend on the batch it is in as far as its trajectory does not."""
     who = "sample"

@@ -3290,6 +3290,18 @@ def _host_ints(who, name, v):
     return t.to(torch.int64)
 
 
+def _state_atoms(who, types, node_ptr, n_types):
+    """what observe_state and vacf_state look at once on the host: (types, node_ptr as int64 host tensors, N, B, T)"""
+    th, ph = _host_ints(who, "types", types), _host_ints(who, "node_ptr", node_ptr)
+    N, B = th.numel(), ph.numel() - 1
+    if B < 0 or (B >= 0 and (int(ph[0]) != 0 or int(ph[-1]) != N or bool((ph[1:] < ph[:-1]).any()))):
+        raise MdlError("%s: node_ptr must start at 0, be non-decreasing and end at N = %d" % (who, N))
+    T = int(n_types) if n_types is not None else (int(th.max()) + 1 if N else 1)
+    if N and (int(th.min()) < 0 or int(th.max()) >= T):
+        raise MdlError("%s: types must be in 0 .. %d (got %d .. %d)" % (who, T - 1, int(th.min()), int(th.max())))
+    return th, ph, N, B, T
+
+
 def observe_state(types, node_ptr, n_types=None, rdf=None, msd=None, device=None):
     """A fresh ObserveState.  types [N] integers in 0 .. n_types - 1 (n_types None: the largest type + 1) and node_ptr [B + 1], arrays
     or tensors: their values are looked at here, once — a device tensor is read back — so that no launch sees a type it cannot
@@ -3298,13 +3310,7 @@ def observe_state(types, node_ptr, n_types=None, rdf=None, msd=None, device=None
     caller's: ops.msd_schedule).  Every argument error raises before a device or the library is asked for anything."""
     who = "observe_state"
     observe_numbers(who, n_types, rdf, msd)
-    th, ph = _host_ints(who, "types", types), _host_ints(who, "node_ptr", node_ptr)
-    N, B = th.numel(), ph.numel() - 1
-    if B < 0 or (B >= 0 and (int(ph[0]) != 0 or int(ph[-1]) != N or bool((ph[1:] < ph[:-1]).any()))):
-        raise MdlError("%s: node_ptr must start at 0, be non-decreasing and end at N = %d" % (who, N))
-    T = int(n_types) if n_types is not None else (int(th.max()) + 1 if N else 1)
-    if N and (int(th.min()) < 0 or int(th.max()) >= T):
-        raise MdlError("%s: types must be in 0 .. %d (got %d .. %d)" % (who, T - 1, int(th.min()), int(th.max())))
+    th, ph, N, B, T = _state_atoms(who, types, node_ptr, n_types)
     rdf, msd = observe_numbers(who, T, rdf, msd)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     st = ObserveState()
@@ -3391,4 +3397,143 @@ def msd_accumulate(pos, lag, mass, state, fixed=None, status=None, remove_com=Tr
     check(lib().mdl_msd_accumulate(ptr(pos), ptr(state.origins), ptr(lag), ptr(mass), ptr(state.types), ptr(fixed), ptr(state.node_ptr),
                                    ptr(status), N, B, K, int(state.n_types), int(state.n_lags), 1 if remove_com else 0, ptr(state.msd_sum),
                                    ptr(state.msd_count), stream()), "mdl_msd_accumulate")
+    return state
+
+
+# ------------------------------------------------------------------------------------------------
+# Time correlations: the on-step velocity and the velocity autocorrelation of a batch, one launch each
+# (csrc/vacf.hip, include/mdl_hip_dynamics.h)
+# ------------------------------------------------------------------------------------------------
+def md_onstep_velocity(vel, force, mass, node_ptr, state, dt, fixed=None, out=None):
+    """The velocity AT the positions `force` was evaluated at, [N, 3] float64, in ONE launch and without a host read
+    (include/mdl_hip_dynamics.h, mdl_md_onstep_velocity).  Between two calls of md_step `vel` lacks the closing half kick of the step;
+    md_step applies it at the start of its next call.  Called between an evaluation and that call, this restates the kick on the same
+    operands: v = fma(dt / 2, (double) force / mass, vel) where state.steps > 0, v = vel where no step has been made, 0 for a fixed atom
+    — bit for bit the velocity whose kinetic energy the next md_step writes to state.ekin, and what its closing call stores.
+      vel [N, 3] float64 and force [N, 3] float32 (contiguous), mass [N] float64, node_ptr [B + 1] int64, state an MDState or an
+      MDCellState (its steps and status are read, nothing is written; under md_cell_step the result is the velocity BEFORE the
+      barostat's 1 / s scaling of that step), dt a number or a [B] float64 tensor, fixed [N] uint8 / bool or None, out [N, 3] float64
+      (contiguous) or None for a new tensor of zeros.
+    The rows of a structure with a non-zero status, or outside every structure, are not written.  Returns out."""
+    who = "md_onstep_velocity"
+    if not isinstance(state, MDState):
+        raise MdlError("%s: state must be an ops.MDState or ops.MDCellState (ops.md_state, ops.md_cell_state)" % who)
+    if not torch.is_tensor(vel) or vel.dtype != torch.float64 or vel.dim() != 2 or vel.shape[1] != 3 or not vel.is_contiguous():
+        raise MdlError("%s: vel must be a contiguous [N, 3] float64 tensor (got %s %s)"
+                       % (who, tuple(getattr(vel, "shape", ())), getattr(vel, "dtype", type(vel))))
+    N = vel.shape[0]
+    if not torch.is_tensor(force) or force.dtype != torch.float32 or tuple(force.shape) != (N, 3) or not force.is_contiguous():
+        raise MdlError("%s: force must be a contiguous [N, 3] float32 tensor with N = %d (got %s %s)"
+                       % (who, N, tuple(getattr(force, "shape", ())), getattr(force, "dtype", type(force))))
+    if not torch.is_tensor(mass) or mass.dtype != torch.float64 or tuple(mass.shape) != (N,) or not mass.is_contiguous():
+        raise MdlError("%s: mass must be a contiguous [N] float64 tensor with N = %d" % (who, N))
+    if not torch.is_tensor(node_ptr) or node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 or node_ptr.numel() < 1 or not node_ptr.is_contiguous():
+        raise MdlError("%s: node_ptr must be a contiguous [B + 1] int64 tensor" % who)
+    B = node_ptr.numel() - 1
+    for k in ("steps", "status"):
+        t = getattr(state, k)
+        if t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise MdlError("%s: state.%s must be a contiguous [%d] int32 tensor (got %s %s)" % (who, k, B, tuple(t.shape), t.dtype))
+    if torch.is_tensor(dt):
+        if dt.dtype != torch.float64 or tuple(dt.shape) != (B,) or not dt.is_contiguous():
+            raise MdlError("%s: dt must be a number or a contiguous [B] float64 tensor with B = %d (got %s %s)" % (who, B, tuple(dt.shape), dt.dtype))
+    elif not float(dt) > 0.0:                                  # (a NaN is not)
+        raise MdlError("%s: dt must be > 0 (got %r)" % (who, dt))
+    if fixed is not None:
+        if not torch.is_tensor(fixed) or fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
+            raise MdlError("%s: fixed must be [N] uint8 or bool with N = %d, or None" % (who, N))
+        fixed = fixed.contiguous().view(torch.uint8)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float64 or tuple(out.shape) != (N, 3) or not out.is_contiguous()):
+        raise MdlError("%s: out must be a contiguous [N, 3] float64 tensor with N = %d, or None" % (who, N))
+    tensors = [force, mass, node_ptr, state.steps, state.status] + [t for t in (dt if torch.is_tensor(dt) else None, fixed, out) if t is not None]
+    require_hip(vel, *tensors)
+    if any(t.device != vel.device for t in tensors):
+        raise MdlError("%s: vel, the other tensors and the state must be on one device" % who)
+    if not torch.is_tensor(dt):
+        dt = torch.full((B,), float(dt), dtype=torch.float64, device=vel.device)
+    if out is None:
+        out = torch.zeros((N, 3), dtype=torch.float64, device=vel.device)
+    check(lib().mdl_md_onstep_velocity(ptr(vel), ptr(force), ptr(mass), ptr(fixed), ptr(node_ptr), ptr(dt), ptr(state.steps), ptr(state.status),
+                                       N, B, ptr(out), stream()), "mdl_md_onstep_velocity")
+    return out
+
+
+def vacf_numbers(who, n_types=None, vacf=None):
+    """The ranges of what a velocity autocorrelation is asked with: dict(n_lags[, origin_every, n_origins, remove_com]), the ranges and
+    defaults of observe_numbers' msd.  Plain numbers, checked before a device or the library is asked for anything.  Returns the dict
+    with every key present, or None."""
+    try:
+        return observe_numbers(who, n_types, None, vacf)[1]
+    except MdlError as e:
+        raise MdlError(str(e).replace("msd", "vacf")) from None
+
+
+class VacfState:
+    """The accumulators of vacf_accumulate, device tensors allocated once (ops.vacf_state):
+      types [N] int32, node_ptr [B + 1] int64, n_types T, n_lags, origins [K, N, 3] float64 (the ring; the caller stores an origin with
+      origins[k].copy_(v)), vacf_sum [B, 2, T, n_lags] float64 (plane 0: the sum of u . u0 per type, plane 1: of m u . u0), vacf_count
+      [B, n_lags] int64."""
+
+    __slots__ = ("types", "node_ptr", "n_types", "n_lags", "origins", "vacf_sum", "vacf_count")
+
+
+def vacf_state(types, node_ptr, n_types=None, vacf=None, device=None):
+    """A fresh VacfState.  types [N] integers in 0 .. n_types - 1 (n_types None: the largest type + 1) and node_ptr [B + 1], arrays or
+    tensors, looked at here once as in observe_state; vacf: dict(n_lags[, origin_every, n_origins]) (the state keeps n_lags and a ring of
+    n_origins slots; the schedule is the caller's: ops.msd_schedule).  Every argument error raises before a device or the library is
+    asked for anything."""
+    who = "vacf_state"
+    if vacf is None:
+        raise MdlError("%s: vacf must be dict(n_lags[, origin_every, n_origins, remove_com])" % who)
+    vacf_numbers(who, n_types, vacf)
+    th, ph, N, B, T = _state_atoms(who, types, node_ptr, n_types)
+    vacf = vacf_numbers(who, T, vacf)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    st = VacfState()
+    st.types = (types.detach().to(dev, torch.int32) if torch.is_tensor(types) else th.to(torch.int32).to(dev)).contiguous()
+    st.node_ptr = (node_ptr.detach().to(dev, torch.int64) if torch.is_tensor(node_ptr) else ph.to(dev)).contiguous()
+    st.n_types, st.n_lags = T, vacf["n_lags"]
+    st.origins = torch.zeros((vacf["n_origins"], N, 3), dtype=torch.float64, device=dev)
+    st.vacf_sum = torch.zeros((B, 2, T, st.n_lags), dtype=torch.float64, device=dev)
+    st.vacf_count = torch.zeros((B, st.n_lags), dtype=torch.int64, device=dev)
+    return st
+
+
+def vacf_accumulate(v, lag, mass, state, fixed=None, status=None, remove_com=True):
+    """One frame into the velocity autocorrelation of a batch against the ring of origins state.origins: ONE launch, no host read
+    (include/mdl_hip_dynamics.h, mdl_vacf_accumulate).
+      v [N, 3] float64, the ON-STEP velocities (ops.md_onstep_velocity); lag [K] int32 ON THE DEVICE, one per slot of the ring: how
+      many samples ago state.origins[k] was stored, negative: skip the slot (a row of ops.msd_schedule's table; live slots must have
+      distinct lags); mass [N] float64; state a VacfState; fixed [N] uint8 / bool or None (fixed atoms are left out); status [B] int32
+      or None: structures with a non-zero status are skipped.
+    With u = v - U and u0 = v0 - U0, U and U0 the velocity of the centre of mass of the structure's free atoms now and at the origin
+    (remove_com) or 0: state.vacf_sum[b, 0, t, lag[k]] += the sum over the free atoms of type t of u . u0, state.vacf_sum[b, 1, t,
+    lag[k]] += that of m u . u0, state.vacf_count[b, lag[k]] += 1.  No atomics: the same bits on every run, alone and in any batch.
+    Returns state."""
+    who = "vacf_accumulate"
+    if not isinstance(state, VacfState):
+        raise MdlError("%s: state must be an ops.VacfState (ops.vacf_state)" % who)
+    if not torch.is_tensor(v) or v.dtype != torch.float64 or v.dim() != 2 or v.shape[1] != 3 or not v.is_contiguous():
+        raise MdlError("%s: v must be a contiguous [N, 3] float64 tensor (got %s %s)"
+                       % (who, tuple(getattr(v, "shape", ())), getattr(v, "dtype", type(v))))
+    N, B, K = state.types.numel(), state.node_ptr.numel() - 1, state.origins.shape[0]
+    if v.shape[0] != N:
+        raise MdlError("%s: v must be [N, 3] with N = %d, the atoms of the state (got %s)" % (who, N, tuple(v.shape)))
+    if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int32 or tuple(status.shape) != (B,)
+                               or not status.is_contiguous()):
+        raise MdlError("%s: status must be a contiguous [B] int32 tensor with B = %d, or None" % (who, B))
+    if not torch.is_tensor(lag) or lag.dtype != torch.int32 or tuple(lag.shape) != (K,) or not lag.is_contiguous():
+        raise MdlError("%s: lag must be a contiguous [K] int32 tensor with K = %d, the slots of state.origins" % (who, K))
+    if not torch.is_tensor(mass) or mass.dtype != torch.float64 or tuple(mass.shape) != (N,) or not mass.is_contiguous():
+        raise MdlError("%s: mass must be a contiguous [N] float64 tensor with N = %d" % (who, N))
+    if fixed is not None:
+        if not torch.is_tensor(fixed) or fixed.dtype not in (torch.uint8, torch.bool) or tuple(fixed.shape) != (N,):
+            raise MdlError("%s: fixed must be [N] uint8 or bool with N = %d, or None" % (who, N))
+        fixed = fixed.contiguous().view(torch.uint8)
+    require_hip(v, lag, mass, fixed, status, state.vacf_sum)
+    if any(t.device != v.device for t in (lag, mass, state.vacf_sum) + tuple(t for t in (fixed, status) if t is not None)):
+        raise MdlError("%s: v, lag, mass, fixed, status and the state must be on one device" % who)
+    check(lib().mdl_vacf_accumulate(ptr(v), ptr(state.origins), ptr(lag), ptr(mass), ptr(state.types), ptr(fixed), ptr(state.node_ptr),
+                                    ptr(status), N, B, K, int(state.n_types), int(state.n_lags), 1 if remove_com else 0, ptr(state.vacf_sum),
+                                    ptr(state.vacf_count), stream()), "mdl_vacf_accumulate")
     return state

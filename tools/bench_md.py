@@ -2,7 +2,7 @@
 """Molecular-dynamics step on the device: what one step of forces.md costs, phase by phase, and the integrator against the same
 update composed from torch ops.
 
-  python tools/bench_md.py [--model cgcnn|schnet] [--graphs 64,1024] [--dim 64] [--steps 20] [--repeats 5] [--seed 0] [--npt] [--observe]
+  python tools/bench_md.py [--model cgcnn|schnet] [--graphs 64,1024] [--dim 64] [--steps 20] [--repeats 5] [--seed 0] [--npt] [--observe] [--vacf]
 
 Structures and model as tools/bench_relax.py takes them; masses uniform in [1, 4], dt = 1, Langevin at gamma = 0.05, kT = 2e-5 (an
 untrained model's forces are of order 1e-3 per A), Maxwell-Boltzmann velocities.  One JSON line per batch size:
@@ -25,7 +25,12 @@ run of its own in which the sampling calls are a fourth phase between rebuild an
   obs_rebuild_ms / obs_evaluate_ms / obs_md_ms   the three phases above in that run: their sum, step_ms, is the un-observed step
   observe_ms        ops.rdf_accumulate + ops.msd_accumulate (and the copy of a new origin) per step, mean over the run, best of repeats
   step_ms / step_observed_ms   the sum without and with observe_ms.  The ring holds 16 origins and is full after 64 samples: use
-                    --steps 80 or more for the steady state"""
+                    --steps 80 or more for the steady state
+--vacf adds what forces.sample costs when a forces.Correlate samples the velocities at EVERY step (every = 1; vacf: 64 lags, a new
+origin every 4 samples; three types), from a run of its own in which the velocity calls are a fourth phase between evaluate and md:
+  vacf_rebuild_ms / vacf_evaluate_ms / vacf_md_ms   the three phases above in that run: their sum, vacf_step_ms, is the un-sampled step
+  vacf_ms           ops.md_onstep_velocity + ops.vacf_accumulate (and the copy of a new origin) per step, mean over the run, best of repeats
+  vacf_step_ms / vacf_step_sampled_ms   the sum without and with vacf_ms; the ring is full after 64 samples, as above"""
 import argparse
 import json
 import os
@@ -139,6 +144,37 @@ def observe_phases(model, packed, steps, seed):
     return [sum(e[k].elapsed_time(e[k + 1]) for e in marks) / steps for k in range(4)]
 
 
+VACF = dict(every=1, vacf=dict(n_lags=64, origin_every=4))
+
+
+def vacf_phases(model, packed, steps, seed):
+    """md_phases with the velocity sampling of forces.sample (a forces.Correlate) at every step as a phase of its own, between
+    evaluate and md where the loop has it: per-step means (ms) of rebuild, evaluate, vacf, md"""
+    ff = forces.ForceField(model, packed, (0.0, 8.0))
+    dev, B = ff.positions.device, ff.node_ptr.numel() - 1
+    mass, dt, gamma, kT, keys = md_inputs(ff, seed)
+    vel = ops.md_velocities(mass, ff.node_ptr, kT, keys)
+    state, n_steps = ops.md_state(B, dev), torch.full((B,), steps, dtype=torch.int32, device=dev)
+    obs = forces._Observer(forces.Correlate(types=np.asarray(packed["numbers"]) % 3, **VACF), packed, steps)
+    obs.start(ff, mass, None, dt, steps, False)
+    marks = []
+    for it in range(steps):
+        e = events(5)
+        e[0].record()
+        ff.rebuild()
+        e[1].record()
+        _, f = ff.evaluate()
+        e[2].record()
+        obs.sample_velocities(it, vel, f, state, dt)
+        e[3].record()
+        ops.md_step(ff.positions, vel, f, mass, ff.node_ptr, state, dt, n_steps, gamma, kT, keys)
+        e[4].record()
+        marks.append(e)
+    torch.cuda.synchronize()
+    assert int(obs.vstate.vacf_count[:, 0].min()) == (steps + 3) // 4
+    return [sum(e[k].elapsed_time(e[k + 1]) for e in marks) / steps for k in range(4)]
+
+
 def integrator_alone(model, packed, repeats, seed, npt=False):
     ff = forces.ForceField(model, packed, (0.0, 8.0))
     dev, B, N = ff.positions.device, ff.node_ptr.numel() - 1, ff.positions.shape[0]
@@ -208,6 +244,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--npt", action="store_true", help="add the step of forces.md_npt to every line")
     ap.add_argument("--observe", action="store_true", help="add the step with forces.sample's sampling at every step to every line")
+    ap.add_argument("--vacf", action="store_true", help="add the step with forces.sample's velocity sampling at every step to every line")
     a = ap.parse_args()
     model = make_model(a, torch.device("cuda"))
     for B in [int(v) for v in a.graphs.split(",")]:
@@ -235,6 +272,15 @@ def main():
             plain = best[0] + best[2] + best[3]
             line.update(obs_rebuild_ms=round(best[0], 3), observe_ms=round(best[1], 4), obs_evaluate_ms=round(best[2], 3),
                         obs_md_ms=round(best[3], 4), step_ms=round(plain, 3), step_observed_ms=round(plain + best[1], 3))
+        if a.vacf:
+            vacf_phases(model, packed, 2, a.seed)
+            best = None
+            for _ in range(a.repeats):
+                t = vacf_phases(model, packed, a.steps, a.seed)
+                best = t if best is None else [min(x, y) for x, y in zip(best, t)]
+            plain = best[0] + best[1] + best[3]
+            line.update(vacf_rebuild_ms=round(best[0], 3), vacf_evaluate_ms=round(best[1], 3), vacf_ms=round(best[2], 4),
+                        vacf_md_ms=round(best[3], 4), vacf_step_ms=round(plain, 3), vacf_step_sampled_ms=round(plain + best[2], 3))
         line.update(integrator_alone(model, packed, a.repeats, a.seed, a.npt))
         print(json.dumps(line), flush=True)
 
