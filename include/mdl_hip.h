@@ -395,7 +395,11 @@ int mdl_linear_act_in(const void* x, const void* y, int xact, const void* w, con
  *   fwd: h[l] receives layer l's output [N, M[l]] (h[NL-1] = y, fp32 rows under dtype | MDL_MLP_F32_IO); the hidden ones are
  *        what the backward needs.
  *   bwd: h[l] (l < NL-1) = the saved hidden outputs, gy = dL/dy [N, M[NL-1]] (fp32 rows under MDL_MLP_F32_IO); dw[l] [M[l], K_l] and db[l] [M[l]] are fp32,
- *        zero-filled by the caller and accumulated with atomics; dx [N, K0] may be NULL. */
+ *        zero-filled by the caller and accumulated with atomics; dx [N, K0] may be NULL.
+ * Accepted: 2 <= K0 <= 64 even, 1 <= M[l] <= 64 (even but for the last); x, every w[l] and every saved h[l] on a 4-byte boundary; gy
+ * on a 4-byte boundary, 2 bytes for bf16 rows of an odd last width.  A shape outside this is MDL_E_UNSUPP, NL outside 1..4, a null
+ * or misaligned pointer, a null dw[l] or N < 0 MDL_E_ARG, each before any launch; N = 0 is MDL_OK and launches nothing.
+ * MDL_DETERMINISTIC (bwd): one workgroup, every dw / db element receives one add. */
 int mdl_mlp_head_fwd(const void* x, const void* const* w, const void* const* b, void* const* h, int64_t N, int K0, int NL,
                      const int* M, int dtype, mdlStream_t stream);
 int mdl_mlp_head_bwd(const void* x, const void* const* w, const void* const* h, const void* gy, void* dx, float* const* dw,

@@ -1873,11 +1873,11 @@ def mlp_head_ok(x, lins, act):
     Any row count: at the reference's batch size (100 graphs, config.yml:136) the layer-by-layer fallback is ~35 launches of
     4-8 us each (library GEMMs, casts, ReLU masks, bias sums) against two."""
     if not (_MLP_HEAD and act == "relu" and x.dtype == torch.bfloat16 and x.is_cuda and x.dim() == 2 and x.is_contiguous()
-            and 1 <= len(lins) <= 4 and x.shape[0] >= 1 and x.shape[1] <= 64 and x.shape[1] % 2 == 0 and x.data_ptr() % 4 == 0):
+            and 1 <= len(lins) <= 4 and x.shape[0] >= 1 and 2 <= x.shape[1] <= 64 and x.shape[1] % 2 == 0 and x.data_ptr() % 4 == 0):
         return False
     k = x.shape[1]
     for j, lin in enumerate(lins):
-        if lin.in_features != k or lin.out_features > 64 or (j + 1 < len(lins) and lin.out_features % 2) or not lin.weight.requires_grad:
+        if lin.in_features != k or not 1 <= lin.out_features <= 64 or (j + 1 < len(lins) and lin.out_features % 2) or not lin.weight.requires_grad:
             return False
         k = lin.out_features
     return True
