@@ -22,7 +22,9 @@ FILE_FLAGS = {"cgconv_ep.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "cfconv.h
               # the same pair distances from the shared csrc/graph_geom.inc, the same bits
               "edge_geom.hip": ["-ffp-contract=off"],
               # the on-step velocity restates one statement of csrc/md.hip: the integrator's bits, so nothing may be contracted
-              "vacf.hip": ["-ffp-contract=off"]}
+              "vacf.hip": ["-ffp-contract=off"],
+              # the structure-factor sums are stated product by product in include/mdl_hip_scattering.h and restated in numpy
+              "sq.hip": ["-ffp-contract=off"]}
 # translation units that #include another .hip file
 FILE_DEPS = {}
 
@@ -40,7 +42,8 @@ def sources():
 
 def _deps_mtime():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("mdl_hip.h", "mdl_hip_analysis.h", "mdl_hip_dynamics.h")]
+    hdrs += [os.path.join(os.path.dirname(HERE), "include", h)
+             for h in ("mdl_hip.h", "mdl_hip_analysis.h", "mdl_hip_dynamics.h", "mdl_hip_scattering.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -167,6 +167,12 @@ DYNAMICS_PROTOTYPES = {
     "mdl_vacf_accumulate": (_i32, [_vp] * 8 + [_i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
 }
 
+# the reciprocal-space layer (include/mdl_hip_scattering.h, csrc/sq.hip): the fourth table
+SCATTERING_PROTOTYPES = {
+    "mdl_density_modes": (_i32, [_vp] * 7 + [_i64, _i64, _i32, _i32] + [_vp] * 4 + [_vp]),
+    "mdl_sq_accumulate": (_i32, [_vp] * 6 + [_i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -183,7 +189,8 @@ def lib():
                 "libmdl_hip.so not found at %s — build it with `python -m matdeeplearn_amd._build` "
                 "(hipcc --offload-arch=gfx950).  matdeeplearn_amd has no CPU/eager fallback." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(ANALYSIS_PROTOTYPES.items()) + list(DYNAMICS_PROTOTYPES.items()):
+        for name, (res, args) in (list(PROTOTYPES.items()) + list(ANALYSIS_PROTOTYPES.items()) + list(DYNAMICS_PROTOTYPES.items())
+                                  + list(SCATTERING_PROTOTYPES.items())):
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
         _lib = handle

@@ -39,7 +39,10 @@ stored frames; no host read, the run's bits unchanged.  Observations holds the a
 diffusion coefficient.  A Correlate is an Observe that also asks for the velocity autocorrelation: the on-step velocity is formed
 from what lies on the device in front of the integrator launch (ops.md_onstep_velocity) and correlated against a ring of origins
 (ops.vacf_accumulate), both csrc/vacf.hip behind include/mdl_hip_dynamics.h; Observations turns the sums into the VACF, the
-vibrational density of states and a Green-Kubo diffusion coefficient."""
+vibrational density of states and a Green-Kubo diffusion coefficient.  A Scatter is a Correlate that also asks for reciprocal space:
+the density modes of every type at reciprocal-lattice vectors of the structure's own cell (ops.density_modes) and their products with
+themselves and with a ring of stored modes (ops.sq_accumulate), both csrc/sq.hip behind include/mdl_hip_scattering.h; Observations
+turns the sums into partial static structure factors S(q) and intermediate scattering functions F(q, t)."""
 import collections
 import inspect
 import math
@@ -847,6 +850,25 @@ class Correlate(Observe):
         self.vacf = ops.vacf_numbers("Correlate", None, vacf)
 
 
+class Scatter(Correlate):
+    """A Correlate that also asks what the trajectory says in reciprocal space: every, skip, rdf, msd, frames_every, types, vacf as
+    Correlate, and
+      sq            None, or dict(q=<[Q, 3] integer array> | n_max=<int >= 1>, fqt=None | dict(n_lags, origin_every[, n_origins]),
+                    max_bytes=2^30): the partial static structure factors S_ab(q) at every sample, and with fqt the partial
+                    intermediate scattering functions F_ab(q, t) at lags of 0 .. n_lags - 1 samples against a ring of time origins
+                    (ranges and defaults as msd).  The wave vectors are reciprocal-lattice vectors q = 2 pi n C^-T of every
+                    structure's own cell, given as integer triples n shared by the batch: q, or with n_max every non-zero triple
+                    with max |n_k| <= n_max of the half space — n is kept if its first non-zero component is positive, n and -n
+                    carry the same information — in lexicographic order, Q = ((2 n_max + 1)^3 - 1) / 2 (ops.sq_half_space).
+                    max_bytes bounds the two large buffers, 8 B P n_lags Q + 16 K B T Q bytes.  At most ops.SQ_MAX_TYPES types.
+    Out of scope: the self part F_s(q, t), total X-ray or neutron weighting of the partials, and structures that are not periodic
+    along all three axes (they would need Cartesian q; they are flagged, Observations.sq_flag, and not counted)."""
+
+    def __init__(self, every=1, skip=0, rdf=None, msd=None, frames_every=0, types=None, vacf=None, sq=None):
+        Correlate.__init__(self, every, skip, rdf, msd, frames_every, types, vacf)
+        self.sq = ops.sq_numbers("Scatter", None, sq)
+
+
 class Observations:
     """What forces.sample recorded: device tensors and small torch helpers.
       hist [B, P, nbins] int64 (ordered pairs (i, j, image) per unordered type pair, P = T (T + 1) / 2), frames [B] int64 (frames
@@ -859,16 +881,22 @@ class Observations:
       With a forces.Correlate: vacf_sum [B, 2, T, n_lags] float64 (plane 0: the sum of u . u0 over the free atoms of a type, plane 1:
       of m u . u0) and vacf_count [B, n_lags] int64 — None without vacf;  frames_vel [F, N, 3] float64, the ON-STEP velocities of the
       stored frames (the rows of a structure that the integrator has stopped are those last formed for it) — None without
-      frames_every or with a plain Observe."""
+      frames_every or with a plain Observe.
+      With a forces.Scatter: qvec [Q, 3] int32 (the integer triples n), sq_sum [B, P, Q] float64 (the sum over the counted frames of
+      Re rho_a conj(rho_b), symmetrised, per unordered pair of types), sq_frames [B] int64, sq_flag [B] int32 (ops.SQ_* bits),
+      cell_sum [B, 9] float64 (the sum of the cells of the counted frames) — None without sq;  fqt_sum [B, P, n_lags, Q] float64 and
+      fqt_count [B, n_lags] int64 — None without sq's fqt."""
 
     def __init__(self, state, species, type_counts, type_totals, frames_pos, frames_cell, frames_step, lag_time, pbc, vacf_state=None,
-                 frames_vel=None):
+                 frames_vel=None, *, qvec=None, sq_sum=None, sq_frames=None, sq_flag=None, cell_sum=None, fqt_sum=None, fqt_count=None):
         self._state, self.species, self.type_counts, self.type_totals = state, species, type_counts, type_totals
         self.frames_pos, self.frames_cell, self.frames_step, self.lag_time, self._pbc = frames_pos, frames_cell, frames_step, lag_time, pbc
         for k in ("hist", "frames", "vol_sum", "flag", "msd_sum", "msd_count", "types", "r_max", "nbins", "n_lags"):
             setattr(self, k, getattr(state, k))
         self.vacf_sum, self.vacf_count = (None, None) if vacf_state is None else (vacf_state.vacf_sum, vacf_state.vacf_count)
         self.frames_vel = frames_vel
+        self.qvec, self.sq_sum, self.sq_frames, self.sq_flag, self.cell_sum = qvec, sq_sum, sq_frames, sq_flag, cell_sum
+        self.fqt_sum, self.fqt_count = fqt_sum, fqt_count
 
     def _asked(self, what, field):
         if field is None:
@@ -961,6 +989,61 @@ class Observations:
         y = self.vacf(t)[:, :lag_hi]
         return (y.sum(1) - 0.5 * (y[:, 0] + y[:, -1])) * self.lag_time / 3.0
 
+    def q(self):
+        """[B, Q, 3] float64: the wave vectors q = 2 pi n (C^-1)^T of every structure, with C = cell_sum / sq_frames, the MEAN cell of
+        the counted frames — exact at constant volume, a choice under NPT (as g takes the mean volume): the modes of every frame
+        were taken at that frame's own reciprocal lattice, the same integers n.  NaN for a structure without a counted frame."""
+        self._asked("q", self.sq_sum)
+        fr = self.sq_frames.double()
+        C = (self.cell_sum / torch.where(fr > 0, fr, torch.full_like(fr, float("nan"))).unsqueeze(1)).view(-1, 3, 3)
+        # the rows of (C^-1)^T are the reciprocal vectors a_j x a_k / det
+        rec = torch.stack([torch.linalg.cross(C[:, (k + 1) % 3], C[:, (k + 2) % 3]) for k in range(3)], 1)
+        rec = rec / (C[:, 0] * rec[:, 0]).sum(1).view(-1, 1, 1)
+        return (2.0 * math.pi) * torch.einsum("qk,bkc->bqc", self.qvec.double(), rec)
+
+    def q_norm(self):
+        """[B, Q] float64: |q| of every wave vector (Observations.q)"""
+        return self.q().norm(dim=2)
+
+    def _sq_norm(self, a, b):
+        n = self.type_totals[:, int(a)].double() * self.type_totals[:, int(b)].double()
+        return torch.where(n > 0, n.sqrt(), torch.full_like(n, float("nan")))
+
+    def sq(self, a, b):
+        """[B, Q] float64: the Ashcroft-Langreth partial structure factor S_ab(q) = < Re rho_a(q) conj(rho_b(q)) > / sqrt(N_a N_b) of
+        types (a, b) at the vectors of qvec: sq_sum / (sq_frames sqrt(N_a N_b)) with N from type_totals (fixed atoms scatter like any
+        other).  NaN for a structure without a counted frame or without atoms of one of the types."""
+        self._asked("sq", self.sq_sum)
+        pair = ops._pair_index(a, b, self.type_totals.shape[1])
+        fr = self.sq_frames.double()
+        n = torch.where(fr > 0, fr, torch.full_like(fr, float("nan"))) * self._sq_norm(a, b)
+        return self.sq_sum[:, pair] / n.unsqueeze(1)
+
+    def sq_radial(self, a, b, q_max, nbins):
+        """(centres [nbins], S [B, nbins]) float64: sq(a, b) averaged over the vectors whose |q| (q_norm) falls into each of nbins
+        shells of width q_max / nbins from 0, per structure; NaN for a shell without a vector"""
+        q_max, nbins = float(q_max), int(nbins)
+        self._asked("sq_radial", self.sq_sum)
+        if not (q_max > 0.0 and q_max < float("inf")) or nbins < 1:
+            raise ops.MdlError("Observations.sq_radial: need q_max > 0, finite, and nbins >= 1 (got %r, %r)" % (q_max, nbins))
+        s, qn = self.sq(a, b), self.q_norm()
+        inside = torch.isfinite(qn) & (qn < q_max)
+        idx = torch.where(inside, (qn * (nbins / q_max)).floor(), torch.zeros_like(qn)).long().clamp_(0, nbins - 1)
+        total = torch.zeros((s.shape[0], nbins), dtype=torch.float64, device=s.device).scatter_add_(1, idx, torch.where(inside, s, torch.zeros_like(s)))
+        count = torch.zeros_like(total).scatter_add_(1, idx, inside.double())
+        centres = (torch.arange(nbins, dtype=torch.float64, device=s.device) + 0.5) * (q_max / nbins)
+        return centres, torch.where(count > 0, total / count, torch.full_like(total, float("nan")))
+
+    def fqt(self, a, b):
+        """[B, n_lags, Q] float64: the partial intermediate scattering function F_ab(q, t) = < Re rho_a(q, t0 + t) conj(rho_b(q, t0)) >
+        / sqrt(N_a N_b), symmetrised in (a, b), at lags of 0 .. n_lags - 1 samples (lag_time each): fqt_sum / (fqt_count sqrt(N_a N_b)).
+        NaN where no sample reached the lag (fqt_count == 0) or the structure has no atoms of one of the types."""
+        self._asked("fqt", self.fqt_sum)
+        pair = ops._pair_index(a, b, self.type_totals.shape[1])
+        c = self.fqt_count.double()
+        n = torch.where(c > 0, c, torch.full_like(c, float("nan"))) * self._sq_norm(a, b).unsqueeze(1)
+        return self.fqt_sum[:, pair] / n.unsqueeze(2)
+
 
 class _Observer:
     """forces.sample's side of _md's hook.  Everything that decides WHEN something is sampled is host arithmetic, done here once:
@@ -982,6 +1065,8 @@ class _Observer:
         self.vacf = ops.vacf_numbers(who, self.T, req.vacf) if isinstance(req, Correlate) else None
         # what _md's second hook is for: only a Correlate can ask, so a plain Observe keeps the launches it had
         self.velocities = isinstance(req, Correlate) and (self.vacf is not None or req.frames_every > 0)
+        # only a Scatter can ask for structure factors: a plain Observe or Correlate keeps the launches it had
+        self.sq = ops.sq_numbers(who, self.T, req.sq, len(node_ptr) - 1) if isinstance(req, Scatter) else None
         self.req, self.node_ptr, self.pbc = req, node_ptr, _host(p["pbc"], np.int32)
         self.sample_of = {it: s for s, it in enumerate(range(req.skip, int(steps) + 1, req.every))}
         self.state = None
@@ -1014,6 +1099,14 @@ class _Observer:
                 self.vslot, self.vlag = slot.tolist(), lag.to(dev)
             if self.req.frames_every > 0:
                 self.frames_vel = torch.full((F, N, 3), float("nan"), dtype=torch.float64, device=dev)
+        self.sstate = None
+        if self.sq is not None:
+            self.sstate = ops.sq_state(self.types, self.node_ptr, self.T, self.sq, dev)
+            self.qslot = self.qlag = None
+            if self.sq["fqt"] is not None:
+                fqt = self.sq["fqt"]
+                slot, lag = ops.msd_schedule(len(self.sample_of), fqt["n_lags"], fqt["origin_every"], fqt["n_origins"])
+                self.qslot, self.qlag = slot.tolist(), lag.to(dev)
 
     def sample_velocities(self, it, vel, force, state, dt):
         """_md's second hook, between the evaluation of step `it` and its integrator launch: the on-step velocity, formed ONCE where
@@ -1047,11 +1140,20 @@ class _Observer:
             if self.slot[s] >= 0:
                 self.state.origins[self.slot[s]].copy_(ff.positions)
             ops.msd_accumulate(ff.positions, self.lag[s], self.mass, self.state, self.fixed, status, self.msd["remove_com"])
+        if self.sstate is not None:
+            # the modes of this frame (one launch), a plain copy where the schedule opens an origin, the products (one launch)
+            ops.density_modes(ff.positions, ff.cell, ff.pbc, self.sstate, status)
+            if self.qslot is not None and self.qslot[s] >= 0:
+                self.sstate.origins[self.qslot[s]].copy_(self.sstate.rho)
+            ops.sq_accumulate(None if self.qlag is None else self.qlag[s], self.sstate, status)
 
     def result(self):
         steps = None if self.frames_step is None else torch.tensor(self.frames_step, dtype=torch.int64, device=self.frames_pos.device)
+        st = self.sstate
+        sq = {} if st is None else dict(qvec=st.qvec, sq_sum=st.sq_sum, sq_frames=st.frames, sq_flag=st.flag, cell_sum=st.cell_sum,
+                                        fqt_sum=st.fqt_sum, fqt_count=st.fqt_count)
         return Observations(self.state, self.species, self.type_counts, self.type_totals, self.frames_pos, self.frames_cell, steps,
-                            self.lag_time, self.pbc, self.vstate, self.frames_vel)
+                            self.lag_time, self.pbc, self.vstate, self.frames_vel, **sq)
 
 
 def sample(model, structs, dist_range, masses, dt, steps, observe, npt=None, **md_kwargs):
@@ -1082,6 +1184,11 @@ def sample(model, structs, dist_range, masses, dt, steps, observe, npt=None, **m
     and a copy.  Under NPT the velocity is the on-step velocity BEFORE the barostat's 1 / s scaling of that step.  Observations.vacf,
     .vdos and .diffusion_gk turn the sums into the correlation function, the vibrational density of states and a Green-Kubo
     diffusion coefficient.  With a plain Observe the launches are what they were.
+    With a forces.Scatter (a Correlate with sq=...) the positions hook of a sampled step also makes one launch for the density modes
+    of every type at the asked reciprocal-lattice vectors (ops.density_modes), a plain copy of them into the ring where the schedule
+    opens an origin, and one launch for the products (ops.sq_accumulate): Observations.sq, .sq_radial, .fqt, .q and .q_norm turn the
+    sums into partial structure factors and intermediate scattering functions.  With a plain Observe or Correlate the launches are
+    what they were.
     Returns (MDResult or NPTResult, Observations).  Counts are integer sums and the displacement sums have no atomics: two calls
     return the same bits, and a structure's observables do not depend on the batch it is in as far as its trajectory does not."""
     who = "sample"

@@ -12,6 +12,7 @@ import collections
 import os
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -3536,4 +3537,207 @@ def vacf_accumulate(v, lag, mass, state, fixed=None, status=None, remove_com=Tru
     check(lib().mdl_vacf_accumulate(ptr(v), ptr(state.origins), ptr(lag), ptr(mass), ptr(state.types), ptr(fixed), ptr(state.node_ptr),
                                     ptr(status), N, B, K, int(state.n_types), int(state.n_lags), 1 if remove_com else 0, ptr(state.vacf_sum),
                                     ptr(state.vacf_count), stream()), "mdl_vacf_accumulate")
+    return state
+
+
+# ------------------------------------------------------------------------------------------------
+# Reciprocal space: the density modes of a batch at a list of reciprocal-lattice vectors and the partial structure factors /
+# intermediate scattering functions formed from them, one launch each per sampled frame
+# (csrc/sq.hip, include/mdl_hip_scattering.h)
+# ------------------------------------------------------------------------------------------------
+# the limits and flag bits of include/mdl_hip_scattering.h, restated here so that a request beyond them is refused before the
+# library is loaded
+SQ_MAX_TYPES = 8
+SQ_NOT_PERIODIC, SQ_NO_VOLUME, SQ_BAD_TYPE, SQ_FATAL = 1, 2, 4, 3
+SQ_MAX_Q = 65535 * 256
+SQ_MAX_BYTES = 2 ** 30
+
+
+def sq_half_space(n_max):
+    """[Q, 3] int32: every non-zero integer triple n with max |n_k| <= n_max whose first non-zero component is positive — n and -n
+    carry the same information —, in lexicographic order; Q = ((2 n_max + 1)^3 - 1) / 2"""
+    n_max = int(n_max)
+    r = range(-n_max, n_max + 1)
+    return np.array([(i, j, k) for i in r for j in r for k in r if (i, j, k) > (0, 0, 0)], np.int32).reshape(-1, 3)
+
+
+def _pair_index(a, b, T):
+    a, b = (int(a), int(b)) if int(a) <= int(b) else (int(b), int(a))
+    if not 0 <= a <= b < T:
+        raise MdlError("pair_index: types must be in 0 .. %d (got %d, %d)" % (T - 1, a, b))
+    return a * T - a * (a - 1) // 2 + (b - a)
+
+
+def sq_numbers(who, n_types=None, sq=None, n_structs=None):
+    """The ranges of what a structure-factor request is asked with — plain numbers, checked before a device or the library is asked
+    for anything.  sq: None, or dict(q=<[Q, 3] integer array> | n_max=<int >= 1>[, fqt=None | dict(n_lags, origin_every[, n_origins]),
+    max_bytes=2^30]).  With n_types and n_structs (B) known, the bytes of the two large buffers, f_sum and the ring of origins,
+    8 B P n_lags Q + 16 K B T Q with P = T (T + 1) / 2, are held against max_bytes.  Returns dict(q, fqt, max_bytes) — q a
+    [Q, 3] int32 numpy array (n_max written out), fqt None or dict(n_lags, origin_every, n_origins): a request itself —, or None."""
+    if n_types is not None and int(n_types) < 1:
+        raise MdlError("%s: the number of types must be >= 1 (got %r)" % (who, n_types))
+    if sq is None:
+        return None
+    form = "dict(q=[Q, 3] integers | n_max=int >= 1[, fqt=dict(n_lags, origin_every[, n_origins]), max_bytes])"
+    if not isinstance(sq, dict) or set(sq) - {"q", "n_max", "fqt", "max_bytes"} or (sq.get("q") is None) == (sq.get("n_max") is None):
+        raise MdlError("%s: sq must be %s, with exactly one of q and n_max (got %s)"
+                       % (who, form, sorted(sq) if isinstance(sq, dict) else type(sq).__name__))
+    if sq.get("n_max") is not None:
+        n_max = sq["n_max"]
+        if isinstance(n_max, bool) or not isinstance(n_max, (int, np.integer)) or n_max < 1:
+            raise MdlError("%s: sq: n_max must be an integer >= 1 (got %r)" % (who, n_max))
+        n_max = int(n_max)
+        if ((2 * n_max + 1) ** 3 - 1) // 2 > SQ_MAX_Q:
+            raise MdlError("%s: sq: n_max = %d gives more than %d vectors" % (who, n_max, SQ_MAX_Q))
+        q = sq_half_space(n_max)
+    else:
+        q = sq["q"]
+        q = np.asarray(q.detach().cpu() if torch.is_tensor(q) else q)
+        if q.ndim != 2 or q.shape[1] != 3 or q.dtype.kind not in "iu":
+            raise MdlError("%s: sq: q must be a [Q, 3] integer array (got %s %s)" % (who, q.shape, q.dtype))
+        if q.size and int(np.abs(q.astype(np.int64)).max()) >= 2 ** 31:
+            raise MdlError("%s: sq: the components of q must fit 32 bits" % who)
+        if q.shape[0] > SQ_MAX_Q:
+            raise MdlError("%s: sq: at most %d vectors (got %d)" % (who, SQ_MAX_Q, q.shape[0]))
+        q = np.ascontiguousarray(q.astype(np.int32))
+    if n_types is not None and int(n_types) > SQ_MAX_TYPES:
+        raise MdlError("%s: sq: at most %d types (got %d)" % (who, SQ_MAX_TYPES, int(n_types)))
+    fqt = sq.get("fqt")
+    if fqt is not None:
+        if not isinstance(fqt, dict) or "remove_com" in fqt:
+            raise MdlError("%s: sq: fqt must be dict(n_lags, origin_every[, n_origins]) (got %r)" % (who, fqt))
+        try:
+            fqt = observe_numbers(who, None, None, fqt)[1]
+        except MdlError as e:
+            raise MdlError(str(e).replace("msd: ", "sq: fqt: ").replace("msd must be dict(n_lags, origin_every[, n_origins, remove_com])",
+                                                                      "sq: fqt must be dict(n_lags, origin_every[, n_origins])")) from None
+        del fqt["remove_com"]
+    max_bytes = sq.get("max_bytes")
+    max_bytes = SQ_MAX_BYTES if max_bytes is None else int(max_bytes)
+    if max_bytes < 0:
+        raise MdlError("%s: sq: max_bytes must be >= 0 (got %r)" % (who, sq["max_bytes"]))
+    if n_types is not None and n_structs is not None and fqt is not None:
+        B, T, Q, K, n_lags = int(n_structs), int(n_types), q.shape[0], fqt["n_origins"], fqt["n_lags"]
+        P = T * (T + 1) // 2
+        need = 8 * B * P * n_lags * Q + 16 * K * B * T * Q
+        if need > max_bytes:
+            raise MdlError("%s: sq: fqt needs 8·B·P·n_lags·Q + 16·K·B·T·Q = %d bytes for f_sum and the ring of origins (B = %d structures, "
+                           "T = %d types, P = %d pairs, Q = %d vectors, n_lags = %d, K = %d origins), more than max_bytes = %d"
+                           % (who, need, B, T, P, Q, n_lags, K, max_bytes))
+    return dict(q=q, fqt=fqt, max_bytes=max_bytes)
+
+
+class SqState:
+    """The buffers of density_modes and sq_accumulate, device tensors allocated once (ops.sq_state):
+      types [N] int32, node_ptr [B + 1] int64, n_types T, qvec [Q, 3] int32 (the integer triples n; q = 2 pi n C^-T), rho [B, T, Q, 2]
+      float64 (the modes of the last frame, (re, im)), frames [B] int64, cell_sum [B, 9] float64, flag [B] int32 (bits SQ_NOT_PERIODIC,
+      SQ_NO_VOLUME, SQ_BAD_TYPE), sq_sum [B, P, Q] float64 with P = T (T + 1) / 2 — the unordered pair (a <= b) at pair_index(a, b);
+      with fqt: n_lags, origins [K, B, T, Q, 2] float64 (the ring; the caller stores an origin with origins[k].copy_(rho)), fqt_sum
+      [B, P, n_lags, Q] float64, fqt_count [B, n_lags] int64 — without: n_lags 0, origins [0, B, T, Q, 2], fqt_sum and fqt_count None."""
+
+    __slots__ = ("types", "node_ptr", "n_types", "qvec", "rho", "frames", "cell_sum", "flag", "sq_sum", "n_lags", "origins", "fqt_sum",
+                 "fqt_count")
+
+    def pair_index(self, a, b):
+        return _pair_index(a, b, self.n_types)
+
+
+def sq_state(types, node_ptr, n_types=None, sq=None, device=None):
+    """A fresh SqState.  types [N] integers in 0 .. n_types - 1 (n_types None: the largest type + 1) and node_ptr [B + 1], arrays or
+    tensors, looked at here once as in observe_state; sq: dict(q | n_max[, fqt, max_bytes]) (ops.sq_numbers; the schedule of the
+    ring is the caller's: ops.msd_schedule).  Every argument error — the byte budget among them — raises before a device or the
+    library is asked for anything and before anything is allocated."""
+    who = "sq_state"
+    if sq is None:
+        raise MdlError("%s: sq must be dict(q | n_max[, fqt, max_bytes])" % who)
+    sq_numbers(who, n_types, sq)
+    th, ph, N, B, T = _state_atoms(who, types, node_ptr, n_types)
+    sq = sq_numbers(who, T, sq, B)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    st = SqState()
+    st.types = (types.detach().to(dev, torch.int32) if torch.is_tensor(types) else th.to(torch.int32).to(dev)).contiguous()
+    st.node_ptr = (node_ptr.detach().to(dev, torch.int64) if torch.is_tensor(node_ptr) else ph.to(dev)).contiguous()
+    st.n_types, st.qvec = T, torch.from_numpy(sq["q"]).to(dev)
+    Q, P = st.qvec.shape[0], T * (T + 1) // 2
+    z = lambda shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
+    st.rho, st.frames, st.cell_sum, st.flag = z((B, T, Q, 2)), z((B,), torch.int64), z((B, 9)), z((B,), torch.int32)
+    st.sq_sum = z((B, P, Q))
+    fqt = sq["fqt"]
+    st.n_lags = 0 if fqt is None else fqt["n_lags"]
+    st.origins = z((0 if fqt is None else fqt["n_origins"], B, T, Q, 2))
+    st.fqt_sum, st.fqt_count = (None, None) if fqt is None else (z((B, P, st.n_lags, Q)), z((B, st.n_lags), torch.int64))
+    return st
+
+
+def _sq_common(who, state, status):
+    if not isinstance(state, SqState):
+        raise MdlError("%s: state must be an ops.SqState (ops.sq_state)" % who)
+    N, B = state.types.numel(), state.node_ptr.numel() - 1
+    T, Q = int(state.n_types), (state.qvec.shape[0] if torch.is_tensor(state.qvec) and state.qvec.dim() == 2 else -1)
+    if T > SQ_MAX_TYPES:
+        raise MdlError("%s: at most %d types (got %d)" % (who, SQ_MAX_TYPES, T))
+    if state.qvec.dtype != torch.int32 or tuple(state.qvec.shape) != (Q, 3) or not state.qvec.is_contiguous():
+        raise MdlError("%s: state.qvec must be a contiguous [Q, 3] int32 tensor (got %s %s)" % (who, tuple(state.qvec.shape), state.qvec.dtype))
+    if state.rho.dtype != torch.float64 or tuple(state.rho.shape) != (B, T, Q, 2) or not state.rho.is_contiguous():
+        raise MdlError("%s: state.rho must be a contiguous [B, T, Q, 2] = %s float64 tensor (got %s %s)"
+                       % (who, (B, T, Q, 2), tuple(state.rho.shape), state.rho.dtype))
+    if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int32 or tuple(status.shape) != (B,)
+                               or not status.is_contiguous()):
+        raise MdlError("%s: status must be a contiguous [B] int32 tensor with B = %d, or None" % (who, B))
+    return N, B, T, Q
+
+
+def density_modes(pos, cell, pbc, state, status=None):
+    """The density modes of one frame of a batch: ONE launch, no host read (include/mdl_hip_scattering.h, mdl_density_modes).
+      pos [N, 3] float64, unwrapped; cell [B, 3, 3] float64, rows are lattice vectors; pbc [B] int32, one bit per periodic axis; state
+      an SqState (its types, node_ptr and qvec are used); status [B] int32 or None: structures with a non-zero status are skipped.
+    state.rho[b, t, q] = the sum over the atoms of type t of exp(-2 pi i n_q . f), f = x C^-1 the fractional coordinates — a plain
+    sum in ascending atom index, one sincospi per term; state.frames[b] += 1 and state.cell_sum[b] += cell[b].  A structure that is
+    not periodic along all three axes or whose cell has no volume gets a bit in state.flag, is not counted and stays out of every
+    later call; its rho, like that of a stopped or empty structure, keeps its bits.  No atomics: the same bits on every run, alone
+    and in any batch.  Returns state."""
+    who = "density_modes"
+    N, B, T, Q = _sq_common(who, state, status)
+    if not torch.is_tensor(pos) or pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 3 or not pos.is_contiguous():
+        raise MdlError("%s: pos must be a contiguous [N, 3] float64 tensor (got %s %s)"
+                       % (who, tuple(getattr(pos, "shape", ())), getattr(pos, "dtype", type(pos))))
+    if pos.shape[0] != N:
+        raise MdlError("%s: pos must be [N, 3] with N = %d, the atoms of the state (got %s)" % (who, N, tuple(pos.shape)))
+    if not torch.is_tensor(cell) or cell.dtype != torch.float64 or tuple(cell.shape) != (B, 3, 3) or not cell.is_contiguous():
+        raise MdlError("%s: cell must be a contiguous [B, 3, 3] float64 tensor with B = %d" % (who, B))
+    if not torch.is_tensor(pbc) or pbc.dtype != torch.int32 or tuple(pbc.shape) != (B,) or not pbc.is_contiguous():
+        raise MdlError("%s: pbc must be a contiguous [B] int32 tensor (one bit per axis) with B = %d" % (who, B))
+    require_hip(pos, cell, pbc, status, state.qvec, state.rho)
+    if any(t.device != pos.device for t in (cell, pbc, state.qvec, state.rho) + (() if status is None else (status,))):
+        raise MdlError("%s: pos, cell, pbc, status and the state must be on one device" % who)
+    check(lib().mdl_density_modes(ptr(pos), ptr(state.types), ptr(state.node_ptr), ptr(cell), ptr(pbc), ptr(status), ptr(state.qvec), N, B, Q,
+                                  T, ptr(state.rho), ptr(state.frames), ptr(state.cell_sum), ptr(state.flag), stream()), "mdl_density_modes")
+    return state
+
+
+def sq_accumulate(lag, state, status=None):
+    """state.rho — the modes density_modes has just written — into the structure factors of a batch: ONE launch, no host read
+    (include/mdl_hip_scattering.h, mdl_sq_accumulate).
+      lag [K] int32 ON THE DEVICE, one per slot of the ring state.origins: how many samples ago origins[k] was stored, negative: skip
+      the slot (a row of ops.msd_schedule's table; live slots must have distinct lags), or None for a state without fqt (K = 0);
+      status [B] int32 or None.
+    Per pair of types (a <= c) and q, with R = rho and O an origin: w = 0.5 ((R_a.re O_c.re + R_a.im O_c.im) + (R_c.re O_a.re + R_c.im
+    O_a.im)); state.sq_sum[b, pair, q] += w of O = R, at every call; state.fqt_sum[b, pair, lag[k], q] += w of O = origins[k, b] and
+    state.fqt_count[b, lag[k]] += 1 for every live slot.  Stopped, empty and fatally flagged structures are skipped.  No atomics, a
+    fixed expression per word: reproducible to the bit.  Returns state."""
+    who = "sq_accumulate"
+    N, B, T, Q = _sq_common(who, state, status)
+    K = state.origins.shape[0]
+    if K == 0:
+        if lag is not None and not (torch.is_tensor(lag) and lag.numel() == 0):
+            raise MdlError("%s: the state has no ring of origins (made without fqt): lag must be None" % who)
+        lag = None
+    elif not torch.is_tensor(lag) or lag.dtype != torch.int32 or tuple(lag.shape) != (K,) or not lag.is_contiguous():
+        raise MdlError("%s: lag must be a contiguous [K] int32 tensor with K = %d, the slots of state.origins" % (who, K))
+    require_hip(state.rho, lag, status, state.sq_sum)
+    if any(t.device != state.rho.device for t in (lag, status) if t is not None):
+        raise MdlError("%s: lag, status and the state must be on one device" % who)
+    check(lib().mdl_sq_accumulate(ptr(state.rho), ptr(state.origins) if K else None, ptr(lag), ptr(state.flag), ptr(status), ptr(state.node_ptr),
+                                  N, B, K, T, Q, max(int(state.n_lags), 1), ptr(state.sq_sum), ptr(state.fqt_sum), ptr(state.fqt_count),
+                                  stream()), "mdl_sq_accumulate")
     return state

@@ -2,7 +2,7 @@
 """Molecular-dynamics step on the device: what one step of forces.md costs, phase by phase, and the integrator against the same
 update composed from torch ops.
 
-  python tools/bench_md.py [--model cgcnn|schnet] [--graphs 64,1024] [--dim 64] [--steps 20] [--repeats 5] [--seed 0] [--npt] [--observe] [--vacf]
+  python tools/bench_md.py [--model cgcnn|schnet] [--graphs 64,1024] [--dim 64] [--steps 20] [--repeats 5] [--seed 0] [--npt] [--observe] [--vacf] [--sq]
 
 Structures and model as tools/bench_relax.py takes them; masses uniform in [1, 4], dt = 1, Langevin at gamma = 0.05, kT = 2e-5 (an
 untrained model's forces are of order 1e-3 per A), Maxwell-Boltzmann velocities.  One JSON line per batch size:
@@ -30,7 +30,15 @@ run of its own in which the sampling calls are a fourth phase between rebuild an
 origin every 4 samples; three types), from a run of its own in which the velocity calls are a fourth phase between evaluate and md:
   vacf_rebuild_ms / vacf_evaluate_ms / vacf_md_ms   the three phases above in that run: their sum, vacf_step_ms, is the un-sampled step
   vacf_ms           ops.md_onstep_velocity + ops.vacf_accumulate (and the copy of a new origin) per step, mean over the run, best of repeats
-  vacf_step_ms / vacf_step_sampled_ms   the sum without and with vacf_ms; the ring is full after 64 samples, as above"""
+  vacf_step_ms / vacf_step_sampled_ms   the sum without and with vacf_ms; the ring is full after 64 samples, as above
+--sq adds what forces.sample costs when a forces.Scatter samples the structure factors at EVERY step (every = 1; sq: n_max = 4, the
+364 vectors of the half space; fqt: 16 lags, a new origin every 4 samples; three types), from a run of its own in which the two
+launches are a fourth phase between rebuild and evaluate, where the loop has them:
+  sq_rebuild_ms / sq_evaluate_ms / sq_md_ms   the three phases above in that run: their sum, sq_step_ms, is the un-sampled step
+  sq_ms             ops.density_modes + ops.sq_accumulate (and the copy of the modes into the ring at a new origin) per step, mean
+                    over the run, best of repeats
+  sq_modes_ms / sq_products_ms   the same two launches alone, the first and the second (with the copy) — their sum is sq_ms
+  sq_step_ms / sq_step_sampled_ms   the sum without and with sq_ms.  The ring holds 4 origins and is full after 16 samples"""
 import argparse
 import json
 import os
@@ -175,6 +183,44 @@ def vacf_phases(model, packed, steps, seed):
     return [sum(e[k].elapsed_time(e[k + 1]) for e in marks) / steps for k in range(4)]
 
 
+SQ = dict(every=1, sq=dict(n_max=4, fqt=dict(n_lags=16, origin_every=4)))
+
+
+def sq_phases(model, packed, steps, seed):
+    """md_phases with the structure-factor sampling of forces.sample (a forces.Scatter) at every step as two phases of their own,
+    between rebuild and evaluate where the loop has them: per-step means (ms) of rebuild, the modes, the products, evaluate, md"""
+    ff = forces.ForceField(model, packed, (0.0, 8.0))
+    dev, B = ff.positions.device, ff.node_ptr.numel() - 1
+    mass, dt, gamma, kT, keys = md_inputs(ff, seed)
+    vel = ops.md_velocities(mass, ff.node_ptr, kT, keys)
+    state, n_steps = ops.md_state(B, dev), torch.full((B,), steps, dtype=torch.int32, device=dev)
+    obs = forces._Observer(forces.Scatter(types=np.asarray(packed["numbers"]) % 3, **SQ), packed, steps)
+    obs.start(ff, mass, None, dt, steps, False)
+    st = obs.sstate
+    marks = []
+    for it in range(steps):
+        e = events(6)
+        e[0].record()
+        ff.rebuild()
+        e[1].record()
+        # what _Observer.sample does for a Scatter, with an event between the two launches
+        s = obs.sample_of[it]
+        ops.density_modes(ff.positions, ff.cell, ff.pbc, st, state.status)
+        e[2].record()
+        if obs.qslot[s] >= 0:
+            st.origins[obs.qslot[s]].copy_(st.rho)
+        ops.sq_accumulate(obs.qlag[s], st, state.status)
+        e[3].record()
+        _, f = ff.evaluate()
+        e[4].record()
+        ops.md_step(ff.positions, vel, f, mass, ff.node_ptr, state, dt, n_steps, gamma, kT, keys)
+        e[5].record()
+        marks.append(e)
+    torch.cuda.synchronize()
+    assert int(st.frames.min()) == steps and int(st.flag.max()) == 0 and int(st.fqt_count[:, 0].min()) == (steps + 3) // 4
+    return [sum(e[k].elapsed_time(e[k + 1]) for e in marks) / steps for k in range(5)]
+
+
 def integrator_alone(model, packed, repeats, seed, npt=False):
     ff = forces.ForceField(model, packed, (0.0, 8.0))
     dev, B, N = ff.positions.device, ff.node_ptr.numel() - 1, ff.positions.shape[0]
@@ -245,6 +291,7 @@ def main():
     ap.add_argument("--npt", action="store_true", help="add the step of forces.md_npt to every line")
     ap.add_argument("--observe", action="store_true", help="add the step with forces.sample's sampling at every step to every line")
     ap.add_argument("--vacf", action="store_true", help="add the step with forces.sample's velocity sampling at every step to every line")
+    ap.add_argument("--sq", action="store_true", help="add the step with forces.sample's structure-factor sampling at every step to every line")
     a = ap.parse_args()
     model = make_model(a, torch.device("cuda"))
     for B in [int(v) for v in a.graphs.split(",")]:
@@ -281,6 +328,16 @@ def main():
             plain = best[0] + best[1] + best[3]
             line.update(vacf_rebuild_ms=round(best[0], 3), vacf_evaluate_ms=round(best[1], 3), vacf_ms=round(best[2], 4),
                         vacf_md_ms=round(best[3], 4), vacf_step_ms=round(plain, 3), vacf_step_sampled_ms=round(plain + best[2], 3))
+        if a.sq:
+            sq_phases(model, packed, 2, a.seed)
+            best = None
+            for _ in range(a.repeats):
+                t = sq_phases(model, packed, a.steps, a.seed)
+                best = t if best is None else [min(x, y) for x, y in zip(best, t)]
+            plain = best[0] + best[3] + best[4]
+            line.update(sq_rebuild_ms=round(best[0], 3), sq_modes_ms=round(best[1], 4), sq_products_ms=round(best[2], 4),
+                        sq_ms=round(best[1] + best[2], 4), sq_evaluate_ms=round(best[3], 3), sq_md_ms=round(best[4], 4),
+                        sq_step_ms=round(plain, 3), sq_step_sampled_ms=round(plain + best[1] + best[2], 3))
         line.update(integrator_alone(model, packed, a.repeats, a.seed, a.npt))
         print(json.dumps(line), flush=True)
 
